@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - train-step views/s (fwd+bwd) of the MI355X rasterizer + LGDWT loss path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c2|c1|c5|tiny]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c2|c1|c5|tiny] [--dump-outputs DIR]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -283,6 +283,42 @@ def valu_roofline(kernel, ms_per_launch, P=None, R=None, counters="sq_insts.json
                           "in this run" % (counters, d.get("tag", "?"), d.get("scene", "C3 workload"))}
 
 
+DUMP_ROWS = 65_536   # model rows written by --dump-outputs: at most 183 floats each (RGB+NIR rows), 48 MB in all
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, tr, loss, rank):
+    """--dump-outputs: what the timed step left its caller after its last step - the loss it returned and the model it
+    updated in place (parameters, Adam moments, densification statistics) - as DIR/<name>.npy, float32 (`rows`: float64).
+    The model is sampled: the same DUMP_ROWS rows, drawn with a fixed seed, in every run.  Every rank calls this (sharded
+    Adam moments are gathered first); rank 0 writes."""
+    import numpy as np
+    tr.gather_optimizer_state()
+    if rank != 0:
+        return
+    m, opt = tr.model, tr.model.optimizer
+    rows = torch.randperm(m.P, generator=torch.Generator().manual_seed(0))[:DUMP_ROWS].sort().values
+    idx = rows.to(m.flat.device)
+    out = {"loss": loss.reshape(()), "rows": rows.double()}
+    for name, p in m.params.items():
+        out[name] = p.detach()[idx]
+    for moment in ("exp_avg", "exp_avg_sq"):
+        for name, v in opt.field_views(getattr(opt, moment)).items():
+            out["%s_%s" % (moment, name)] = v[idx]
+    for name in ("xyz_gradient_accum", "denom", "max_radii2D"):
+        out[name] = getattr(m, name)[idx]
+    if m.nir_gain is not None:
+        out["nir_gain"] = m.nir_gain.detach().reshape(())
+    arrays = {k: v.detach().cpu().numpy() for k, v in out.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -291,7 +327,11 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage-timers", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -511,12 +551,18 @@ def main():
     for i in range(args.steps):
         if sampled:  # the dominant kernel's event pair (~10 us of pipeline drain) rides on every 4th step of the region
             api.call("profile_enable", 1 if i % 4 == 0 else 0)
-        run_step(k)
+        last_loss = run_step(k)
         k += 1
     settle()  # (the last step's deferred verdict: inside the timed region)
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:   # (before the untimed legs below step the model further)
+        if graphed is not None:   # (a replay that settle() found invalid was taken again eagerly: its loss is here)
+            last_loss = graphed.s_loss
+        names_ = dump_outputs(args.dump_outputs, tr, last_loss, rank)
+        if names_:
+            log("outputs of the last timed step: %d arrays in %s" % (len(names_), args.dump_outputs))
     # the exchange brackets of the TIMED steps only (the stage-timer passes and the other legs below step the model too)
     timed_exchange_events = []
     if world > 1:

@@ -2,7 +2,7 @@
 # The un-profiled bench lines of a round, one gpurun call:  bash profiles/bench_all.sh r05
 # writes gpurun_out/bench_<tag>/<tag>_bench_<config>.json (copy them into profiles/), the stderr logs beside them.
 TAG=${1:-rXX}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/bench_$TAG
 mkdir -p $OUT
 cd $R

@@ -1,7 +1,8 @@
 """Developer tool: which binning path (regions / LSD) the C2-size train step takes on its limited views, and its stage times.
    python tests/tools/c2_binning_probe.py"""
 import os, sys
-sys.path.insert(0, "/root/repo/sparse-view-3dgs-pack_amd"); sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(ROOT, "sparse-view-3dgs-pack_amd")); sys.path.insert(0, ROOT)
 import torch, bench
 from gsplat_amd import hip_backend
 from gsplat_amd._lib import hip_api
