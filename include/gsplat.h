@@ -322,7 +322,8 @@ typedef struct GsStepState {
    * ranks by the caller); max_radii2D is updated in place as always.  fail_flag (device, may be NULL): set to 1.0f when
    * the forward had flagged overflow or trunc_failed - the call then writes ZERO statistic increments and no gradients -
    * else to 0.0f; reduced (sum) with the gradients it tells every rank whether any rank's view was invalid
-   * (gs_adam_step_gated takes it as its gate). */
+   * (gs_adam_step_gated takes it as its gate).  The single-GPU form writes the same flag when fail_flag is given (the gate of
+ * the trained exposures' step, gs_exposure_adam). */
   float* grad_out[5];
   float* fail_flag;
   /* ---- two-phase step (single GPU; any list mode) ----
@@ -691,6 +692,30 @@ int gs_rows_pack(const float* flat, int32_t P, int32_t nfields, const int32_t* w
                  const int32_t* pos, int32_t K, float* packed, void* stream);
 int gs_rows_unpack(float* flat, int32_t P, int32_t nfields, const int32_t* widths /*host*/, const uint8_t* mask,
                    const int32_t* pos, int32_t K, const float* packed, void* stream);
+/* ---- image stage of the train step (LGDWT-GS/train.py:117-124 + gaussian_renderer/__init__.py:112-119): what happens to the
+ * render between the rasterizer and the loss.  raw / pred / g_pred / g_raw: [3,H,W] planes; exposure: the camera's [3,4]
+ * row (12 device floats, row-major), NULL = none; alpha: [H,W] device floats, NULL = all ones.  All buffers distinct.
+ *   forward : lin[j] = sum_c raw[c] E[c][j] + E[j][3];  pred = clamp(lin, 0, 1) * alpha     (exposure, clamp, mask)
+ *   backward: g_lin[j] = g_pred[j] * alpha * [0 <= lin[j] <= 1];  g_raw[c] = sum_j E[c][j] g_lin[j];
+ *             partials (may be NULL) = one row of 12 per workgroup (gs_image_stage_partials_count(H, W) rows, all written):
+ *             word 4 c + j = sum raw[c] g_lin[j], word 4 j + 3 = sum g_lin[j] - the workgroup's share of dL/dE.
+ * g_pred is the criterion's gradient with respect to pred WITHOUT its clamp fold (gs_ssim_bwd_uniform: clamp_src = NULL).
+ * float4 along x when H*W is a multiple of 4 and the planes 16-byte aligned; any size works. */
+int64_t gs_image_stage_partials_count(int32_t H, int32_t W);
+int gs_image_stage_fwd(const float* raw, const float* exposure, const float* alpha, int32_t H, int32_t W, float* pred,
+                       void* stream);
+int gs_image_stage_bwd(const float* raw, const float* exposure, const float* alpha, const float* g_pred, int32_t H, int32_t W,
+                       float* g_raw, float* partials, void* stream);
+/* The trained exposures' optimizer (torch.optim.Adam over the [n_cameras,3,4] tensor, LGDWT-GS/scene/gaussian_model.py:201)
+ * in ONE launch of one workgroup.  partials != NULL: the n_partials rows of gs_image_stage_bwd are added in a fixed order
+ * (double) into the gradient of camera `camera`'s row; every other row's gradient is 0; the whole gradient is written to
+ * grad when grad != NULL.  partials == NULL: the gradient is read from grad.  exposure != NULL: one Adam step (1-based `step`,
+ * bias-corrected, lr, betas, eps as torch; the betas in double, as torch has them for 1 - beta) over all 12 n_cameras elements with that gradient - rows with a zero gradient
+ * move as torch moves them; exp_avg / exp_avg_sq required.  exposure == NULL: gradient only (grad required).
+ * gate: as gs_adam_step_gated - device float, may be NULL; when *gate != 0 nothing is written at all. */
+int gs_exposure_adam(const float* partials, int64_t n_partials, int32_t camera, float* grad, float* exposure, float* exp_avg,
+                     float* exp_avg_sq, int32_t n_cameras, float lr, double beta1, double beta2, float eps, int32_t step,
+                     const float* gate, void* stream);
 /* mask[i] = 1 when Gaussian i emitted instances in the forward whose geometry state `scratch` holds (what gs_backward_step's
  * data-parallel form writes into GsStepState.grad_mask later - available as soon as the forward's geometry phase has run,
  * so the union of the ranks' masks can be exchanged while the loss and the backward are still running). */

@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_step_kernel(Prepro
   // the forward ran out of binning capacity (possible only when the caller did not re-run it: a replayed graph): the
   // image was not rendered, so nothing may be updated - the host sees the flag and repeats the step eagerly
   const bool failed = (sa.hdr->overflow | sa.hdr->trunc_failed) != 0u;
-  if (grads_out && st.fail_flag && blockIdx.x == 0 && threadIdx.x == 0) *st.fail_flag = failed ? 1.0f : 0.0f;
+  if (st.fail_flag && blockIdx.x == 0 && threadIdx.x == 0) *st.fail_flag = failed ? 1.0f : 0.0f;
   if (failed) {
     // (the rows the blend backward accumulated into for this invalid view were cleaned by chain_kernel)
     if (grads_out && st.max_radii2D) {  // this view contributes no statistics (the sum over ranks must stay finite)

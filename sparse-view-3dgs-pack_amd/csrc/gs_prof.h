@@ -30,6 +30,7 @@ enum GsStage {
   ST_TILE_ORDER,
   ST_STEP_UNINST,
   ST_CHAIN,
+  ST_IMAGE_STAGE,
   ST_COUNT
 };
 

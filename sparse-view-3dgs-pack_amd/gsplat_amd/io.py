@@ -441,6 +441,27 @@ def composite_rgba(rgba_u8, white_background):
     return np.transpose(q.astype(np.float32) / 255.0, (2, 0, 1))
 
 
+def camera_alpha_mask(image, train_test_exp=False, is_test_view=False, is_test_dataset=False):
+    """Camera.alpha_mask of scene/cameras.py:43-54 for a [C,H,W] image in [0,1] (PILtoTorch's layout, C = 3 or 4): the alpha
+    channel when there is one, else ones -> float32 [1,H,W].  With train_test_exp, a test view keeps half of itself: the
+    test set's copy zeroes the left half (columns < W // 2), the training set's copy the right half.  The trainer's
+    `alpha_masks` take these (on the device)."""
+    import torch
+    img = torch.as_tensor(image)
+    if img.dim() != 3 or img.shape[0] not in (3, 4):
+        raise ValueError("image: [3,H,W] or [4,H,W], got %s" % (tuple(img.shape),))
+    if img.shape[0] == 4:
+        mask = img[3:4].to(torch.float32).clone()
+    else:
+        mask = torch.ones_like(img[0:1], dtype=torch.float32)
+    if train_test_exp and is_test_view:
+        if is_test_dataset:
+            mask[..., :mask.shape[-1] // 2] = 0
+        else:
+            mask[..., mask.shape[-1] // 2:] = 0
+    return mask
+
+
 def nerfpp_norm(cam_infos):
     """getNerfppNorm (dataset_readers.py:48-69) -> dict(translate, radius)."""
     centers = []

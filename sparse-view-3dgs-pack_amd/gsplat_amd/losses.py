@@ -288,13 +288,16 @@ class LossOps:
 class FusedLGDWTLoss(torch.autograd.Function):
     """The whole criterion of LGDWT-GS/train.py:128-202 as ONE autograd node on the un-clamped render.
 
+    stage (optional, _ImageStage): the trained exposure and the alpha mask of LGDWT-GS/train.py:117-124 applied first, by
+              gs_image_stage_fwd (pred = clamp(raw . E + b, 0, 1) * alpha); the criterion then runs on pred, and its image
+              gradient goes back through gs_image_stage_bwd (which also leaves the exposure's per-workgroup sums behind).
     forward : clamp(0,1) -> L1 sum, SSIM sum (+ the three derivative maps), eight DWT band sums, three patch sums
               -> gs_lgdwt_combine (loss, running-mean DWT scale and the backward coefficients, all on the device)
     backward: three kernels accumulate into ONE image-gradient buffer; the last one folds in the clamp mask.
     No torch elementwise pass over an image, no host synchronisation."""
 
     @staticmethod
-    def forward(ctx, ops, raw, gt, mask, sums, running_mean, params):
+    def forward(ctx, ops, raw, gt, mask, sums, running_mean, params, stage=None):
         """sums: the camera's persistent 16-float accumulator (LGDWTCriterion.sums_for): words 0..12 are zero on entry -
         gs_lgdwt_combine_p re-zeroes them after reading (GsLgdwtParams.reset_sums) - and word 13 holds the number of
         selected patches; so neither a fill nor a copy kernel runs per step."""
@@ -302,6 +305,10 @@ class FusedLGDWTLoss(torch.autograd.Function):
         raw, gt = _c(raw), _c(gt)
         Cc, H, W = raw.shape
         st = _stream(raw)
+        if stage is not None:   # exposure -> clamp -> alpha; everything below sees pred (clamping it again changes nothing)
+            stage.raw = raw
+            raw = torch.empty_like(raw)
+            api.call("image_stage_fwd", stage.raw.data_ptr(), _p(stage.exposure), _p(stage.alpha), H, W, raw.data_ptr(), st)
         d1, d2, d3 = torch.empty_like(raw), torch.empty_like(raw), torch.empty_like(raw)
         # the patch term rides on the global DWT kernels when the sizes allow (its sums are level-1 band differences of the
         # same 2 x 2 blocks, restricted to the selected patches): two launches less per step
@@ -339,7 +346,7 @@ class FusedLGDWTLoss(torch.autograd.Function):
                  None if dwt_part is None else dwt_part.data_ptr(), 0 if dwt_part is None else dwt_part.numel() // 12,
                  None if l1_part is None else l1_part.data_ptr(), 0 if l1_part is None else l1_part.numel(),
                  running_mean.data_ptr(), C.byref(params.c), out.data_ptr(), st)
-        ctx.ops, ctx.params, ctx.patch_folded = ops, params, patch_folded
+        ctx.ops, ctx.params, ctx.patch_folded, ctx.stage = ops, params, patch_folded, stage
         ctx.save_for_backward(raw, img, gt, mask, d1, d2, d3, out)
         ctx.mark_non_differentiable(out)
         ctx.set_materialize_grads(False)   # no zero tensor for the unused gradient of `out`
@@ -349,7 +356,7 @@ class FusedLGDWTLoss(torch.autograd.Function):
     def backward(ctx, g, _gout):
         raw, img, gt, mask, d1, d2, d3, out = ctx.saved_tensors
         if g is None:
-            return (None,) * 7
+            return (None,) * 8
         api, params = ctx.ops.api, ctx.params
         Cc, H, W = raw.shape
         st = _stream(raw)
@@ -372,13 +379,47 @@ class FusedLGDWTLoss(torch.autograd.Function):
         hook = getattr(ctx.ops, "before_last_backward_kernel", None)
         if hook is not None:   # (the train step's side launch, RasterBackend.UNINST_AT = "ssim_backward")
             hook()
+        stage = getattr(ctx, "stage", None)
         api.call("ssim_bwd_uniform", img.data_ptr(), gt.data_ptr(), 1, Cc, H, W, coef[1:].data_ptr(), d1.data_ptr(),
-                 d2.data_ptr(), d3.data_ptr(), grad.data_ptr(), 1, raw.data_ptr() if params.clamp else None, st)
-        return None, grad, None, None, None, None, None
+                 d2.data_ptr(), d3.data_ptr(), grad.data_ptr(), 1,
+                 raw.data_ptr() if params.clamp and stage is None else None, st)
+        if stage is not None:   # (the clamp's gradient is folded in here, with the mask and the exposure)
+            g_raw = torch.empty_like(grad)
+            api.call("image_stage_bwd", stage.raw.data_ptr(), _p(stage.exposure), _p(stage.alpha), grad.data_ptr(), H, W,
+                     g_raw.data_ptr(), _p(stage.partials), st)
+            if stage.exposure_grad is not None:
+                api.call("exposure_adam", stage.partials.data_ptr(), stage.partials.numel() // 12, 0,
+                         stage.exposure_grad.data_ptr(), None, None, None, 1, 0.0, 0.0, 0.0, 0.0, 0, None, st)
+            grad = g_raw
+        return None, grad, None, None, None, None, None, None
 
 
 def ctx_ps(params):
     return int(params.patch_size)
+
+
+class _ImageStage:
+    """What FusedLGDWTLoss applies before its criterion: the camera's exposure row E [3,4] and the alpha mask [H,W] (either
+    may be None), the buffer of the exposure's per-workgroup gradient sums, and where to add them up (None: the caller does,
+    e.g. with the exposure optimizer's one launch, ExposureAdam.step_from_partials)."""
+
+    def __init__(self, api, exposure, alpha, exposure_grad, H, W, device):
+        self.exposure = None if exposure is None else _c(exposure.detach())
+        if self.exposure is not None and self.exposure.numel() != 12:
+            raise ValueError("exposure: the camera's [3,4] row")
+        self.alpha = None
+        if alpha is not None:
+            if alpha.numel() != H * W:
+                raise ValueError("alpha mask of %s for a %d x %d image" % (tuple(alpha.shape), W, H))
+            self.alpha = _c(alpha.detach().reshape(H, W))
+        self.partials = None
+        if self.exposure is not None:
+            n = int(api.raw("image_stage_partials_count")(H, W))
+            self.partials = torch.empty((n * 12,), dtype=torch.float32, device=device)
+        if exposure_grad is not None and (exposure_grad.numel() != 12 or not exposure_grad.is_contiguous()):
+            raise ValueError("exposure_grad: a contiguous [3,4] row (e.g. grad[camera] of the [n,3,4] gradient)")
+        self.exposure_grad = exposure_grad
+        self.raw = None
 
 
 class _FusedParams:
@@ -462,9 +503,15 @@ class LGDWTCriterion:
                 pass
         return s
 
-    def fused_call(self, raw_image, gt_image, mask=None, manual_ctx=None):
+    def fused_call(self, raw_image, gt_image, mask=None, manual_ctx=None, exposure=None, alpha=None, exposure_grad=None):
         """Criterion on the rasterizer's raw output (the clamp of gaussian_renderer/__init__.py:119 is applied -
         and differentiated - inside).  Returns (loss, parts) like __call__.
+        exposure: the camera's trained [3,4] exposure row (gaussian_renderer/__init__.py:112-115), alpha: its [H,W] / [1,H,W]
+        mask (train.py:121-124); with either, gs_image_stage_* run around the criterion's kernels: loss(clamp(raw . E + b) *
+        alpha), and the gradient returned for raw_image is through all of it.  The exposure's gradient is not an autograd
+        output: exposure_grad (a contiguous [3,4] row, e.g. grad[ci] of the [n,3,4] gradient buffer) receives it in the
+        backward; without exposure_grad its per-workgroup sums stay in parts["exposure_partials"] after the backward
+        (ExposureAdam.step_from_partials adds them up and steps in one launch).  Neither given: exactly the plain criterion.
         manual_ctx: an object that stands in for the autograd context - the node's forward runs under no_grad and the caller
         calls FusedLGDWTLoss.backward(manual_ctx, seed, None) itself (gsplat_amd.trainer: the train step without the autograd
         engine)."""
@@ -484,13 +531,19 @@ class LGDWTCriterion:
             if mask is None:
                 mask = self._no_mask[dev] = torch.zeros((1,), dtype=torch.uint8, device=dev)
             sums = self.sums_for(None, dev)
+        stage = None
+        if exposure is not None or alpha is not None:
+            stage = _ImageStage(self.ops.api, exposure, alpha, exposure_grad, key[1], key[2], dev)
         if manual_ctx is not None:
             with torch.no_grad():
-                loss, out = FusedLGDWTLoss.forward(manual_ctx, self.ops, raw_image, gt_image, mask, sums, self.dwt_running_mean, fp)
+                loss, out = FusedLGDWTLoss.forward(manual_ctx, self.ops, raw_image, gt_image, mask, sums, self.dwt_running_mean, fp,
+                                                   stage)
         else:
-            loss, out = FusedLGDWTLoss.apply(self.ops, raw_image, gt_image, mask, sums, self.dwt_running_mean, fp)
+            loss, out = FusedLGDWTLoss.apply(self.ops, raw_image, gt_image, mask, sums, self.dwt_running_mean, fp, stage)
         parts = {"l1": out[5], "ssim": out[6], "dwt": out[2], "dwt_scale": out[4], "patch": out[3], "base": out[1],
                  "running_mean_before": out[7:8]}
+        if stage is not None and stage.partials is not None:
+            parts["exposure_partials"] = stage.partials
         return loss, parts
 
     def __call__(self, image, gt_image, mask=None):

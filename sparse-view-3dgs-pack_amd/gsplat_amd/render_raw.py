@@ -97,9 +97,12 @@ class _RawRender(torch.autograd.Function):
 
 
 def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_sh=False, override_color=None,
-           use_trained_exp=False, camera_key=None):
+           use_trained_exp=False, camera_key=None, defer_exposure=False):
     """gaussian_renderer/__init__.py:18-128.  camera_key (optional, not in the reference): a stable identity of the camera - the
-    backend then keeps its tile order and verified depth limits between visits."""
+    backend then keeps its tile order and verified depth limits between visits.
+    defer_exposure (with use_trained_exp; not in the reference): skip the torch matmul of :112-115 and return the camera's
+    [3,4] row as "exposure" - for lgdwt_loss.criterion().fused_call(pkg["render_unclamped"], gt, exposure=pkg["exposure"],
+    alpha=..., exposure_grad=...), which applies it (and the clamp, and the alpha mask) in its own kernels."""
     from diff_gaussian_rasterization import GaussianRasterizationSettings, _RasterizeGaussians
     if override_color is not None or getattr(pipe, "compute_cov3D_python", False) or getattr(pipe, "convert_SHs_python", False):
         raise NotImplementedError("render_raw serves the rasterizer's own SH / covariance path only "
@@ -117,10 +120,16 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_
         prefiltered=False, debug=bool(getattr(pipe, "debug", False)), antialiasing=bool(getattr(pipe, "antialiasing", False)))
     rendered_image, radii, depth_image = _RawRender.apply(xyz, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
                                                           pc._rotation, screenspace_points, rs, backend, camera_key)
-    if use_trained_exp:   # gaussian_renderer/__init__.py:112-115
+    exposure = None
+    if use_trained_exp and defer_exposure:
+        exposure = pc.get_exposure_from_name(viewpoint_camera.image_name)
+    elif use_trained_exp:   # gaussian_renderer/__init__.py:112-115
         exposure = pc.get_exposure_from_name(viewpoint_camera.image_name)
         rendered_image = torch.matmul(rendered_image.permute(1, 2, 0), exposure[:3, :3]).permute(2, 0, 1) + exposure[:3, 3, None, None]
     # one key more than the reference's dict: the render BEFORE the clamp of gaussian_renderer/__init__.py:119, for
     # lgdwt_loss.criterion().fused_call(), which applies - and differentiates - the clamp inside its one node
-    return {"render": rendered_image.clamp(0, 1), "render_unclamped": rendered_image, "viewspace_points": screenspace_points,
-            "visibility_filter": (radii > 0).nonzero(), "radii": radii, "depth": depth_image}
+    out = {"render": rendered_image.clamp(0, 1), "render_unclamped": rendered_image, "viewspace_points": screenspace_points,
+           "visibility_filter": (radii > 0).nonzero(), "radii": radii, "depth": depth_image}
+    if defer_exposure:
+        out["exposure"] = exposure
+    return out

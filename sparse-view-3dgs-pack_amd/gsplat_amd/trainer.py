@@ -403,10 +403,16 @@ class GaussianModelLite:
     def enable_exposure(self, n_cameras):
         """Per-camera exposure (LGDWT-GS/scene/gaussian_model.py:173-176,201: a [n_cams, 3, 4] parameter starting at
         [I | 0] with its own Adam; rate from get_expon_lr_func(0.01, 0.001, delay_steps 0, delay_mult 0) over the
-        run, arguments/__init__.py:87-90, set by update_learning_rate).  Used by render(..., use_trained_exp=True)."""
+        run, arguments/__init__.py:87-90, set by update_learning_rate).  Used by render(..., use_trained_exp=True).
+        A GPU model built with an api gets the device optimizer (optim.ExposureAdam: one launch per step, gated like the
+        model's own step, so the fast train step keeps its shape); otherwise torch's."""
         eye = torch.eye(3, 4, device=self.device)[None].repeat(int(n_cameras), 1, 1)
         self.exposure = torch.nn.Parameter(eye.requires_grad_(True))
-        self.exposure_optimizer = torch.optim.Adam([self.exposure])
+        if isinstance(self.optimizer, FlatAdam) and self.exposure.is_cuda:
+            from .optim import ExposureAdam
+            self.exposure_optimizer = ExposureAdam(self.exposure)
+        else:
+            self.exposure_optimizer = torch.optim.Adam([self.exposure])
 
     def get_exposure(self, camera_index):
         return self.exposure[camera_index]
@@ -894,6 +900,7 @@ class TrainOptions:
         self.depth_l1_weight_final = 0.01
         self.optimizer_type = "default"   # arguments/__init__.py:101 ("sparse_adam": Trainer(optimizer_type=...))
         self.white_background = False
+        self.random_background = False    # arguments/__init__.py: a fresh torch.rand(3) background every iteration (train.py:117)
         self.cameras_extent = 1.0         # scene.cameras_extent = getNerfppNorm radius (dataset_readers.py:48-69)
         self.seed = 0
         for k, v in kw.items():
@@ -913,7 +920,8 @@ class Trainer:
     `train_iteration(it, opt)` is one iteration of the reference's loop with its schedule."""
 
     def __init__(self, model, cameras, gt_images, criterion, Rasterizer, Settings, bg, rank=0, world_size=1,
-                 optimizer_step=True, masks=None, sharded_optimizer=None, sparse_exchange=None, optimizer_type="default"):
+                 optimizer_step=True, masks=None, sharded_optimizer=None, sparse_exchange=None, optimizer_type="default",
+                 alpha_masks=None):
         # sharded_optimizer (default: env GS_SHARDED_ADAM=1): reduce-scatter the gradients, Adam on this rank's 1/N of
         # the rows, all-gather the parameters - instead of all-reduce + the full Adam pass on every replica
         import os
@@ -944,6 +952,10 @@ class Trainer:
         self.rank, self.world_size = rank, world_size
         self.optimizer_step = optimizer_step
         self.masks = masks  # per-camera ELF patch masks (depend on the ground truth only): cached
+        # per-camera Camera.alpha_mask (scene/cameras.py:43-54, io.camera_alpha_mask): [1,H,W] / [H,W] on the model's device,
+        # or None for the whole list - train.py:121-124 multiplies the render by it before the loss
+        self.alpha_masks = alpha_masks
+        self._bg_gen = None   # opt.random_background: the device generator and the one buffer GsView.bg points at
         # Depth regularisation (train.py:204-216): per camera None or (mono_invdepth [1,H,W], depth_mask [1,H,W] or None) - the
         # reference's viewpoint_cam.invdepthmap / depth_mask of a camera with depth_reliable (scene/cameras.py:60-80) - and the
         # current weight (train_iteration sets it from the schedule of train.py:69; 0 = term off)
@@ -984,6 +996,9 @@ class Trainer:
         return mine
 
     densify_decisions = None
+    alpha_masks = None
+    _bg_gen = None
+    _use_stage = False   # (set per step by _step_camera: exposure / alpha mask inside the criterion's node)
 
     def train_iteration(self, iteration, opt):
         """One iteration (1-based) of LGDWT-GS/train.py:97-288: LR schedule, SH ramp, camera draw, render + loss +
@@ -1002,6 +1017,8 @@ class Trainer:
         if self.depth_priors is not None:   # train.py:69
             self.depth_l1_weight = expon_lr(iteration, opt.depth_l1_weight_init, opt.depth_l1_weight_final, max_steps=opt.iterations)
         ci = self.draw_cameras(opt.seed)
+        if opt.random_background:   # train.py:117 (after sync: a repeated step has used the previous iteration's colour)
+            self._draw_background(opt.seed)
         # What the schedule will do after the backward is known beforehand, so the optimizer step can run inside the
         # step (fused into the backward on one GPU, overlapped with the all-reduce on several).  Its order against
         # reset_opacity is free: the reset replaces the opacity row and its moments, the step skips exactly that row.
@@ -1028,6 +1045,34 @@ class Trainer:
             m.reset_opacity()
             reset = True
         return dict(loss=loss, densified=densified, reset=reset, P=m.P, camera=ci)
+
+    def _draw_background(self, seed):
+        """A fresh rand(3) into the one persistent background buffer (allocated, with a generator seeded from seed + rank on
+        the buffer's device, the first time): no allocation, no host synchronisation per iteration."""
+        if self._bg_gen is None:
+            dev = self.bg.device if torch.is_tensor(self.bg) else torch.device(self.model.device)
+            self._bg_gen = torch.Generator(device=dev)
+            self._bg_gen.manual_seed(int(seed) + self.rank)
+            self.bg = torch.empty((3,), dtype=torch.float32, device=dev)
+        torch.rand((3,), out=self.bg, generator=self._bg_gen)
+
+    def _alpha(self, ci):
+        return None if self.alpha_masks is None else self.alpha_masks[ci]
+
+    def _image_extras(self):
+        """Does the step touch the image between rasterizer and loss (trained exposure, alpha mask, random background)?"""
+        return self.model.exposure is not None or self.alpha_masks is not None or self._bg_gen is not None
+
+    def _stage_ok(self):
+        """Can the fast step (manual backward, deferred depth limits) take this trainer's exposure / alpha masks, through the
+        image stage (gs_image_stage_*) and the device exposure optimizer?  TrainerNIR (its own render and criterion) and
+        optimizer_type "sparse_adam" are not wired to it: with an exposure, alpha masks or a random background they keep
+        the slow form - the torch exposure of render(), the mask multiplied in torch, no deferred verdict."""
+        from .optim import ExposureAdam
+        m = self.model
+        return (self.optimizer_type != "sparse_adam" and type(self)._render_view is Trainer._render_view
+                and type(self)._criterion_backward is Trainer._criterion_backward
+                and (m.exposure is None or isinstance(m.exposure_optimizer, ExposureAdam)))
 
     # single-GPU steps run the optimizer inside the rasterizer backward (gs_backward_step); GS_FUSED_STEP=0 keeps the
     # separate activation-backward / statistics / Adam kernels (the path every multi-GPU step takes)
@@ -1082,9 +1127,11 @@ class Trainer:
             return
         opt = self.model.optimizer
         opt.t, opt.seg_steps = p["counters"][0], dict(p["counters"][1])
+        if p.get("exposure_steps") is not None:   # (its gated step changed nothing on the device either)
+            self.model.exposure_optimizer.steps = p["exposure_steps"]
         if p["running_mean"] is not None:
             self.criterion.dwt_running_mean.copy_(p["running_mean"])
-        p["loss"].copy_(self._step_camera(p["ci"], True, p["skip"]))  # (the camera's limits are invalid now: full lists)
+        p["loss"].copy_(self._step_camera(p["ci"], True, p["skip"], exposure_step=p.get("exposure_step")))  # (the camera's limits are invalid now: full lists)
         self.sync()
 
     def checkpoint(self):
@@ -1121,7 +1168,7 @@ class Trainer:
 
     def _manual_step_ok(self, fused_step, fused):
         fn = getattr(self.Rasterizer, "_fn", None)
-        return (self.MANUAL_BACKWARD and fused_step and fused and self.model.exposure is None and fn is not None
+        return (self.MANUAL_BACKWARD and fused_step and fused and (not self._image_extras() or self._stage_ok()) and fn is not None
                 and getattr(getattr(fn, "_impl", None), "backend", None) is not None
                 and type(self)._render_view is Trainer._render_view and type(self)._criterion_backward is Trainer._criterion_backward)
 
@@ -1146,7 +1193,8 @@ class Trainer:
             color, radii, depth = fn.forward(rctx, p["xyz"], None, p["features"], empty, p["opacity"], p["scaling"], p["rotation"],
                                              empty, rs)
             verdict = backend.take_deferred() if deferred else None
-            loss, parts = self.criterion.fused_call(color, self.gts[ci], mask=mask, manual_ctx=lctx)
+            loss, parts = self.criterion.fused_call(color, self.gts[ci], mask=mask, manual_ctx=lctx,
+                                                    exposure=None if m.exposure is None else m.exposure[ci], alpha=self._alpha(ci))
             grad_depth = None
             prior = self._depth_prior(ci)
             if prior is not None:   # train.py:204-216: one launch gives the term and its inverse-depth image gradient
@@ -1164,7 +1212,7 @@ class Trainer:
     def _render_view(self, ci, fused, raw):
         m = self.model
         return render(self.cameras[ci], m, self.Rasterizer, self.Settings, self.bg, filter_as_indices=None,
-                      clamp=not fused, fused=True, use_trained_exp=m.exposure is not None, camera_index=ci,
+                      clamp=not fused, fused=True, use_trained_exp=m.exposure is not None and not self._use_stage, camera_index=ci,
                       raw_activations=raw, camera_key=("trainer", self.uid, ci))
 
     def _depth_prior(self, ci):
@@ -1182,6 +1230,17 @@ class Trainer:
 
     def _criterion_backward(self, pkg, ci, mask, fused, side_launch):
         """-> (loss, parts); runs the backward.  side_launch: callable that issues the two-phase step's side launch (or None)"""
+        alpha = self._alpha(ci)
+        if self._use_stage:   # exposure and mask in the criterion's node (gs_image_stage_*); the exposure's sums in parts
+            m = self.model
+            loss, parts = self.criterion.fused_call(pkg["render"], self.gts[ci], mask=mask,
+                                                    exposure=None if m.exposure is None else m.exposure.detach()[ci], alpha=alpha)
+            loss, parts = self._depth_term(pkg, ci, loss, parts)
+            self._arm_side_launch(side_launch)
+            torch.autograd.backward(loss, self.criterion.ops.unit_grad(loss.device))
+            return loss, parts
+        if alpha is not None:   # train.py:121-124 in torch: image = clamp(render) * alpha_mask
+            pkg = dict(pkg, render=(pkg["render"].clamp(0, 1) if fused else pkg["render"]) * alpha.reshape(pkg["render"].shape[-2:]))
         if fused:
             loss, parts = self.criterion.fused_call(pkg["render"], self.gts[ci], mask=mask)
             loss, parts = self._depth_term(pkg, ci, loss, parts)
@@ -1226,10 +1285,15 @@ class Trainer:
         backend = self._backend()
         fused_step = self._fused_step_ok(backend, optimizer_step)
         fused_dp = self._fused_dp_ok(backend, optimizer_step)
-        # (not with a trainable exposure: its torch optimizer has stepped on the invalid image by the time the verdict
-        # arrives, and a repeat would step it twice)
+        fused = getattr(self.criterion, "fused", False)
+        # exposure / alpha mask through the image stage: the exposure's step is a gated device launch (ExposureAdam), so a
+        # view whose limits fail changes nothing and is repeated like any other.  Without the stage (TrainerNIR, sparse_adam,
+        # the unfused forms) a trainable exposure keeps the eager form: torch has stepped it before the verdict arrives.
+        stage_ok = self._stage_ok()
+        self._use_stage = bool(fused and (fused_step or fused_dp) and stage_ok
+                               and (m.exposure is not None or self.alpha_masks is not None))
         deferred = (fused_step or fused_dp) and self.depth_limit == "deferred" and getattr(self, "_coef_dev", None) is None \
-            and m.exposure is None
+            and (not self._image_extras() or stage_ok)
         if deferred:
             counters = (m.optimizer.t, dict(m.optimizer.seg_steps))
             backend.depth_limit_request = "defer"
@@ -1244,12 +1308,16 @@ class Trainer:
             rows = getattr(self, "rows_override", None)  # parity tests: blend sums to use instead of stage 1
             if rows is not None:
                 backend.fused_step.rows_override = rows.data_ptr()
+            if self._use_stage and m.exposure is not None:   # the backward writes the view's verdict: the exposure's gate
+                backend.fused_step.fail_flag = m.exposure_optimizer.gate.data_ptr()
         elif backend is not None and hasattr(backend, "grad_arena") and not m.with_nir:
             m.arm_grad_arena(backend)
-        fused = getattr(self.criterion, "fused", False)
         mask = None if self.masks is None else self.masks[ci]
         rm = None
+        path = "fused" if (fused_step or fused_dp) else "unfused"
+        exp_steps = m.exposure_optimizer.steps if (self._use_stage and m.exposure is not None) else None
         if self.RAW_ACTIVATIONS and self._manual_step_ok(fused_step, fused):
+            path = "manual"
             # (the deferred verdict of THIS forward is picked up inside: the backend parks it when the forward returns)
             pkg, loss, parts, verdict = self._manual_step(ci, mask, backend, deferred)
         else:
@@ -1289,11 +1357,12 @@ class Trainer:
                 if fused:
                     rm = parts.get("running_mean_before")
                 self._pending = dict(verdict=verdict, flag_host=host, event=ev, ci=ci, skip=skip, counters=counters,
-                                     running_mean=rm, loss=loss.detach())
+                                     running_mean=rm, loss=loss.detach(), exposure_steps=exp_steps, exposure_step=exposure_step)
         elif verdict is not None:
             if fused:  # (the criterion's combine kernel leaves the running mean it started from in its output: no clone)
                 rm = parts.get("running_mean_before")
-            self._pending = dict(verdict=verdict, ci=ci, skip=skip, counters=counters, running_mean=rm, loss=loss.detach())
+            self._pending = dict(verdict=verdict, ci=ci, skip=skip, counters=counters, running_mean=rm, loss=loss.detach(),
+                                 exposure_steps=exp_steps, exposure_step=exposure_step)
         if fused_dp:
             pass
         elif fused_step:
@@ -1303,7 +1372,23 @@ class Trainer:
                 raise RuntimeError("fused train step armed but the rasterizer backward did not run")
         else:
             self._unfused_tail(pkg, radii, optimizer_step, skip)
-        if m.exposure_optimizer is not None:
+        partials = parts.get("exposure_partials") if self._use_stage else None
+        if partials is not None:
+            # the image stage left camera ci's gradient as per-workgroup sums: one launch adds them up and steps (gated by
+            # the view's verdict: the backward's flag on one GPU, the reduced one on N)
+            eo = m.exposure_optimizer
+            gate = m.fail_flag if fused_dp else eo.gate
+            if self.world_size > 1:
+                eo.grad_row(partials, ci)
+                dist.all_reduce(m.exposure.grad, op=dist.ReduceOp.SUM)
+                if exposure_step:
+                    eo.step(gate=gate)
+            elif exposure_step:
+                eo.step_from_partials(partials, ci, gate=gate)
+            else:
+                eo.grad_row(partials, ci)
+            eo.zero_grad(set_to_none=True)
+        elif m.exposure_optimizer is not None:
             # train.py:280-281: the exposure optimizer steps with the main one; a camera's row is only touched by the
             # rank that rendered it, the others hold a zero gradient for it (N > 1: summed like every other gradient)
             if m.exposure.grad is not None:
@@ -1312,7 +1397,7 @@ class Trainer:
                 if exposure_step:
                     m.exposure_optimizer.step()
             m.exposure_optimizer.zero_grad(set_to_none=True)
-        self.last = dict(loss=loss.detach(), radii=radii, parts=parts)
+        self.last = dict(loss=loss.detach(), radii=radii, parts=parts, path=path)
         return loss.detach()
 
     DP_CHUNKS = 4
@@ -2048,9 +2133,10 @@ class GraphedStep:
         self.settle()
         ci = tr.camera_index(k)
         be = self._backend()
-        if tr.model.exposure is not None or not tr._fused_step_ok(be, True) or be._capacity_hint <= 0 or \
+        if tr._image_extras() or not tr._fused_step_ok(be, True) or be._capacity_hint <= 0 or \
                 tr._depth_prior(ci) is not None:
-            # what the capture cannot hold (a torch optimizer for the exposure, N > 1, the depth term's weight - a kernel
+            # what the capture cannot hold (an exposure, alpha masks or a random background - not wired into the capture -,
+            # N > 1, the depth term's weight - a kernel
             # argument that changes every iteration - ...), or no view has been rendered yet to size the binning capacity from
             self.eager_steps += 1
             self.s_loss = tr._step_camera(ci, True, ())
