@@ -593,8 +593,11 @@ __global__ void export_geom_kernel(GeomView g, int P, float* depths, float* mean
                                    float* rgb, uint8_t* clamped, uint32_t* tiles_touched, uint32_t* point_offsets) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
-  const Splat sp = g.splat[i];
-  const bool vis = sp.rect_max != 0;  // a visible Gaussian has a non-empty tile rectangle (maxx >= 1)
+  // a visible Gaussian has a non-empty tile rectangle (maxx >= 1).  With depth limits, one whose pairs were all cut has no record
+  // of this forward (what lies there belongs to an earlier one): it is reported as not visible, every exported field 0
+  const bool unwritten = g.hdr->pad[HDR_LIMITED] != 0u && g.tiles_touched[i] == 0u;
+  const Splat sp = unwritten ? Splat{} : g.splat[i];
+  const bool vis = sp.rect_max != 0;
   if (depths) depths[i] = vis ? sp.depth : 0.f;
   if (means2D) {
     means2D[2 * i] = vis ? sp.x : 0.f;

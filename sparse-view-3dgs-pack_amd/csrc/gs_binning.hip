@@ -46,12 +46,15 @@ __global__ void __launch_bounds__(GS_BLOCK) bin_prepare_kernel(GeomHeader* hdr, 
 // host's bound: the partition of the region entries is launched for the binning CAPACITY (instances) but sorts a fifth of that
 // many entries, and a workgroup beyond the last tile used to write its 512 zero counts into a 4.5 x larger table (94 MB of
 // scattered 4-byte writes per pass at C3, profiles/r05_binning_counters.csv).
+// n = min(*n_dev, n_bound): the grid, the table and the key arrays are sized for the host's bound n_bound, so a device count
+// above it (a scan over broken counts) must not index past them; the caller detects such a count (tb_regions_kernel).
 template <int BITS>
 __global__ void __launch_bounds__(RS_HIST_THREADS) rs_hist_kernel(const uint32_t* __restrict__ keys, const uint32_t* n_dev,
-                                                                  int shift, uint32_t* __restrict__ hist, int drop_max) {
+                                                                  uint32_t n_bound, int shift, uint32_t* __restrict__ hist,
+                                                                  int drop_max) {
   constexpr int RADIX = 1 << BITS;
   __shared__ uint32_t h[RS_HIST_THREADS / 64][RADIX];  // one private histogram per wave
-  const uint32_t n = *n_dev;
+  const uint32_t n = min(*n_dev, n_bound);
   const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;
   if (blockIdx.x >= nblk) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -125,10 +128,10 @@ __global__ void __launch_bounds__(1024) scan_sums_kernel(uint32_t* sums, int nb)
 // the workgroups of the sort) and stores the row total; the scatter kernel adds the exclusive scan of the 256
 // totals itself.  (The generic three-kernel scan of the whole table cost two more launches per pass.)
 __global__ void __launch_bounds__(GS_BLOCK) rs_rowscan_kernel(uint32_t* __restrict__ hist, const uint32_t* __restrict__ n_dev,
-                                                              uint32_t* __restrict__ totals) {
+                                                              uint32_t n_bound, uint32_t* __restrict__ totals) {
   constexpr int IT = 8;
   __shared__ uint32_t wsum[GS_BLOCK / 64];
-  const uint32_t nblk = (*n_dev + RS_TILE - 1) / RS_TILE;
+  const uint32_t nblk = (min(*n_dev, n_bound) + RS_TILE - 1) / RS_TILE;
   uint32_t* row = hist + (size_t)blockIdx.x * nblk;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   uint32_t carry = 0;
@@ -171,7 +174,7 @@ template <int NT, int BITS>
 __global__ void __launch_bounds__(NT) rs_scatter_kernel(const uint32_t* __restrict__ kin,
                                                         const uint32_t* __restrict__ vin,  // NULL: value = index
                                                         uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                        const uint32_t* n_dev, int shift,
+                                                        const uint32_t* n_dev, uint32_t n_bound, int shift,
                                                         const uint32_t* __restrict__ hist,
                                                         const uint32_t* __restrict__ totals, int drop_max,
                                                         uint32_t* __restrict__ n_kept) {
@@ -180,7 +183,7 @@ __global__ void __launch_bounds__(NT) rs_scatter_kernel(const uint32_t* __restri
   constexpr int ITEMS = RS_TILE / NT;       // keys per thread = ranking rounds per wave
   static_assert(NT >= RADIX && RS_TILE % NT == 0, "one thread per digit in phase 2");
   __shared__ uint32_t s_hist[NW][RADIX];  // phase 1: wave digit counts; phase 3: output bases
-  const uint32_t n = *n_dev;
+  const uint32_t n = min(*n_dev, n_bound);   // (see rs_hist_kernel)
   const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;   // (the table's row stride: see rs_hist_kernel)
   const uint32_t t0 = blockIdx.x * RS_TILE;
   if (t0 >= n) return;
@@ -308,7 +311,9 @@ int launch_bin_prepare(const GeomView& g, int64_t capacity, uint2* ranges, int T
 // Twelve launches of ~4.8 us each are pure launch latency at that size (58 of the 515 us of a C1 step); here the 16 waves
 // keep all keys in registers (16 per lane, wave w owns the contiguous slice [1024 w, 1024 w + 1024)), rank them per pass
 // with the same ballot multi-split as rs_scatter_kernel and exchange them through LDS.  Same stable LSD passes, same
-// result bit for bit.
+// result bit for bit.  The keys 0xFFFFFFFF (Gaussians without instances) are sorted along - to the end, the sort is stable and
+// they are the largest keys - but not counted: n_kept is the number of the others, as after the first pass of the multi-pass
+// form, so nothing downstream visits a Gaussian whose record this forward may not have written (gs_preprocess.hip).
 // ------------------------------------------------------------------------------------------------------------------
 #define RS_SMALL_ITEMS 16
 #define RS_SMALL_MAX (1024 * RS_SMALL_ITEMS)
@@ -320,18 +325,23 @@ __global__ void __launch_bounds__(1024) rs_small_sort_kernel(const uint32_t* __r
   __shared__ uint32_t s_key[RS_SMALL_MAX];
   __shared__ uint32_t s_val[RS_SMALL_MAX];
   __shared__ uint32_t s_wtot[RS_RADIX / 64];
+  __shared__ uint32_t s_kept;
   const uint32_t n = min(*n_dev, (uint32_t)RS_SMALL_MAX);
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (n_kept && tid == 0) *n_kept = n;  // (nothing is dropped at this size: Gaussians without instances sort to the end)
+  if (tid == 0) s_kept = 0;
+  __syncthreads();
   const unsigned long long lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   const uint32_t w0 = (uint32_t)wid * (64 * ITEMS);
   uint32_t key[ITEMS], val[ITEMS], pre[ITEMS];
+  uint32_t kept = 0;  // (wave-uniform)
 #pragma unroll
   for (int r = 0; r < ITEMS; r++) {
     const uint32_t i = w0 + r * 64 + lane;
     key[r] = i < n ? kin[i] : 0xFFFFFFFFu;
     val[r] = i;
+    kept += (uint32_t)__popcll(__ballot(key[r] != 0xFFFFFFFFu));
   }
+  if (lane == 0 && kept) atomicAdd(&s_kept, kept);
   for (int shift = 0; shift < end_bit; shift += RS_BITS) {
     for (int k = tid; k < NW * RS_RADIX; k += NT) (&s_hist[0][0])[k] = 0;
     __syncthreads();
@@ -405,6 +415,8 @@ __global__ void __launch_bounds__(1024) rs_small_sort_kernel(const uint32_t* __r
       vout[i] = val[r];
     }
   }
+  __syncthreads();
+  if (n_kept && tid == 0) *n_kept = s_kept;
 }
 
 // digit_bits: 8, or 9 for a sort that is then ONE pass over keys below 512 (the partition of the region entries at 1080p:
@@ -422,14 +434,15 @@ int launch_radix_sort(const SortBufs& b, const uint32_t* n_dev, int64_t n_bound,
     return 0;
   }
   const uint32_t nblk = (uint32_t)((n_bound + RS_TILE - 1) / RS_TILE);
+  const uint32_t nb32 = n_bound > 0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)n_bound;
   if (digit_bits == 9) {
     if (end_bit > 9 || first_keys != nullptr) return GS_E_SHAPE;
-    hipLaunchKernelGGL(rs_hist_kernel<9>, dim3(nblk), dim3(RS_HIST_THREADS), 0, s, b.keys[cur], n_dev, 0, b.hist, 0);
+    hipLaunchKernelGGL(rs_hist_kernel<9>, dim3(nblk), dim3(RS_HIST_THREADS), 0, s, b.keys[cur], n_dev, nb32, 0, b.hist, 0);
     GS_LAUNCH_CHECK(s, debug);
-    hipLaunchKernelGGL(rs_rowscan_kernel, dim3(512), dim3(GS_BLOCK), 0, s, b.hist, n_dev, b.scan_tmp);
+    hipLaunchKernelGGL(rs_rowscan_kernel, dim3(512), dim3(GS_BLOCK), 0, s, b.hist, n_dev, nb32, b.scan_tmp);
     GS_LAUNCH_CHECK(s, debug);
     hipLaunchKernelGGL((rs_scatter_kernel<RS_SCATTER_THREADS, 9>), dim3(nblk), dim3(RS_SCATTER_THREADS), 0, s, b.keys[cur], b.vals[cur],
-                       b.keys[cur ^ 1], b.vals[cur ^ 1], n_dev, 0, b.hist, b.scan_tmp, 0, (uint32_t*)nullptr);
+                       b.keys[cur ^ 1], b.vals[cur ^ 1], n_dev, nb32, 0, b.hist, b.scan_tmp, 0, (uint32_t*)nullptr);
     GS_LAUNCH_CHECK(s, debug);
     return 0;
   }
@@ -442,14 +455,14 @@ int launch_radix_sort(const SortBufs& b, const uint32_t* n_dev, int64_t n_bound,
     const uint32_t* kin = ext ? first_keys : b.keys[cur];
     const uint32_t* vin = ext ? nullptr : b.vals[cur];
     const int drop = ext && n_kept ? 1 : 0;  // the first pass of the depth sort filters (see rs_hist_kernel)
-    hipLaunchKernelGGL(rs_hist_kernel<RS_BITS>, dim3(nblk), dim3(RS_HIST_THREADS), 0, s, kin, n_dev, shift, b.hist, drop);
+    hipLaunchKernelGGL(rs_hist_kernel<RS_BITS>, dim3(nblk), dim3(RS_HIST_THREADS), 0, s, kin, n_dev, nb32, shift, b.hist, drop);
     GS_LAUNCH_CHECK(s, debug);
-    hipLaunchKernelGGL(rs_rowscan_kernel, dim3(RS_RADIX), dim3(GS_BLOCK), 0, s, b.hist, n_dev, b.scan_tmp);
+    hipLaunchKernelGGL(rs_rowscan_kernel, dim3(RS_RADIX), dim3(GS_BLOCK), 0, s, b.hist, n_dev, nb32, b.scan_tmp);
     GS_LAUNCH_CHECK(s, debug);
     // 512 threads per 4096-key tile (8 ranking rounds per wave): 0.213 ms for the two instance passes against 0.226 with
     // 256 threads and 0.217 with 1024 - the pass is bound by one workgroup's dependent chain, not by throughput
     hipLaunchKernelGGL((rs_scatter_kernel<RS_SCATTER_THREADS, RS_BITS>), dim3(nblk), dim3(RS_SCATTER_THREADS), 0, s, kin, vin,
-                       b.keys[cur ^ 1], b.vals[cur ^ 1], n_dev, shift, b.hist, b.scan_tmp, drop, drop ? n_kept : nullptr);
+                       b.keys[cur ^ 1], b.vals[cur ^ 1], n_dev, nb32, shift, b.hist, b.scan_tmp, drop, drop ? n_kept : nullptr);
     GS_LAUNCH_CHECK(s, debug);
     if (drop) n_dev = n_kept;  // the later passes see the survivors only
     cur ^= 1;

@@ -39,8 +39,11 @@ struct GeomHeader {
   uint32_t step_tag;      // word 8: GsScratch.step_tag as gs_forward_status found it
   uint32_t pad[55];       // pad[0] = word 9: GS_STATUS_CHECK over (step_tag, num_rendered, overflow, trunc_failed)
                           // pad[HDR_SIDE_CURSOR]: next Gaussian block of step_uninstanced_kernel (zeroed with the header)
+                          // pad[HDR_LIMITED]: 1 if the geometry phase ran with depth limits - then a Gaussian with
+                          // tiles_touched == 0 may have no record of this forward (gs_preprocess.hip), 0 otherwise
 };
 #define HDR_SIDE_CURSOR 1
+#define HDR_LIMITED 2
 static_assert(sizeof(GeomHeader) == 256, "header is one 256-B block");
 
 // 64-byte per-Gaussian record written by the forward preprocess kernel.

@@ -134,6 +134,7 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
   asm volatile("" : "+v"(op_in), "+v"(sc_in.x), "+v"(sc_in.y), "+v"(sc_in.z), "+v"(rq_in.x), "+v"(rq_in.y), "+v"(rq_in.z),
                "+v"(rq_in.w));
   const GsLdsFloatPtr lds_seg = (GsLdsFloatPtr)s_limit + (GS_LIMIT_TILES_IN_LDS ? T : 0);
+  if (idx == 0) g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
   if (idx < a.P) {
     Splat sp;
     sp.x = sp.y = sp.depth = sp.invdepth = 0.f;
@@ -296,7 +297,10 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
               }
             }
           }
-          if (!a.tile_depth_limit) entries = hull > tiles ? (rowwise | 0x8000u) : hull;
+          // (15 bits of count: a larger one - a hull of more than 32 766 regions, images above ~11.6 k x 11.6 k - is left to
+          //  the binning to count, as tb_rect_entries leaves it)
+          if (!a.tile_depth_limit)
+            entries = (hull > TB_ENTRIES_MAX || rowwise > TB_ENTRIES_MAX) ? TB_ENTRIES_UNKNOWN : (hull > tiles ? (rowwise | 0x8000u) : hull);
           if (a.tile_depth_limit && tiles) {
             // The verdict travels to the duplicate kernel in the record (bits 8-9 of `clamped`): 0 nothing cut, 1 all,
             // 2 cut by the exact rule (Gaussians inside a 4 x 4 tile box: their <= 16 bounds fetched at once, rows then
@@ -388,7 +392,9 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
     } while (false);
 
     // a Gaussian the depth limits removed entirely leaves no record and no covariance behind: nothing downstream reads
-    // them (it is not in the depth order, no list names it, and the backward skips it on tiles_touched == 0)
+    // them (its depth key is 0xFFFFFFFF, so it is not in the depth order - n_ordered counts the other keys at both sort sizes -,
+    // no list names it, the backward skips it on tiles_touched == 0, and gs_export_geom reports it as invisible: see
+    // HDR_LIMITED)
     const bool write_record = !(a.tile_depth_limit && tiles == 0 && radius_out > 0);
     if (write_record) {
       float4* dst = reinterpret_cast<float4*>(&g.splat[idx]);

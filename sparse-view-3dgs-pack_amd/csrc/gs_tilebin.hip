@@ -11,7 +11,9 @@
 // Gaussian covers its tiles in blocks, so the unit that has to travel through a partition is not the instance but the
 // (Gaussian, 4 x 4-tile REGION) pair with a 16-bit tile mask: ~6 instances each at C3.
 //
-//   1. depth order of the P Gaussians (gs_binning.hip: 4 LSD passes over 8 B x P, Gaussians without instances dropped);
+//   1. depth order of the P Gaussians (gs_binning.hip: 4 LSD passes over 8 B x P, or one workgroup for P <= 16 384; Gaussians
+//      without instances are dropped at both sizes - hdr->n_ordered counts the rest -, so every record read below was written
+//      by this forward: with depth limits, preprocess writes none for a Gaussian whose pairs were all cut);
 //   2. tb_entries_kernel + scan + tb_emit_kernel: in depth order, every Gaussian emits one 8-byte ENTRY per region its tiles
 //      reach: key = region id | tile mask << 16, value = Gaussian index (bit 4 k + c of the mask = tile (4 ry + k, 4 rx + c));
 //   3. a stable partition of the entries by region id (rs_* of gs_binning.hip; 1-2 passes over 8 B x entries, 4-6 x fewer

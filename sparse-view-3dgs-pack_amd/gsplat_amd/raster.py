@@ -410,6 +410,10 @@ class RasterBackend:
     # the stream hand-offs cost more than the hidden stream saves); GS_TWO_PHASE_STEP=0 switches it off.
     # depth-limited lists for callers that name their cameras (GaussianRasterizer.camera_key); GS_KEYED_LIMITS=0: never
     force_rowwise_entries = False
+    # test hook: called as scratch_fill(kind, tensor) right after each fresh scratch buffer of rasterize_gaussians is allocated
+    # (kind "geom", "img", "binning"), so that a test decides what the buffer holds before the forward runs instead of the
+    # caching allocator (tests/test_gpu_scratch_reuse.py); None: nothing happens
+    scratch_fill = None
     KEYED_LIMITS = os.environ.get("GS_KEYED_LIMITS", "1") != "0"
     # region-binned forwards whose verdict is collected later (deferred eager steps, replayed graphs): the status block is
     # written into the pinned host block by the forward's own last kernel (GsScratch.status_host) instead of by a copy
@@ -595,9 +599,13 @@ class RasterBackend:
         stream = self._stream(device)
 
         gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
+        fill = self.scratch_fill
         geom = torch.empty((gb,), **u8)
         self._raw_geom = geom.data_ptr() if raw else None
         img = torch.empty((ib,), **u8)
+        if fill is not None:
+            fill("geom", geom)
+            fill("img", img)
         empty = torch.empty((0,), **u8)
         # (the train step's side launch and its backward describe the same view and the same Gaussians: they take these
         #  structs - and the tensors `keep` holds alive - instead of building them again; keyed by this forward's geometry buffer)
@@ -607,6 +615,8 @@ class RasterBackend:
         def new_binning(cap):
             _, _, bb, _ = self.scratch_bytes(P, W, H, cap)
             binning = torch.empty((bb,), **u8)
+            if fill is not None:
+                fill("binning", binning)
             self._remember_capacity(binning, cap)
             return binning
 

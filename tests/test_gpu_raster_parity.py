@@ -38,7 +38,9 @@ def reference_lists(hip):
     hip.tile_cull = old
 
 
-def forward_state(backend, scene, cam, device, bg, antialiasing):
+def forward_state(backend, scene, cam, device, bg, antialiasing, buffers=None):
+    """-> the forward's outputs and exported state (host tensors); `buffers` (a dict) also receives the forward's own
+    scratch tensors (geom, binning, img)"""
     def dev(t):
         return None if t is None else t.to(device)
     e = torch.empty(0)
@@ -51,6 +53,8 @@ def forward_state(backend, scene, cam, device, bg, antialiasing):
             cam.image_height, cam.image_width, sh if sh is not None else e, scene.get("sh_degree", 0),
             cam.camera_center.to(device), False, antialiasing, False)
     R, color, radii, geom, binning, img, invd = backend.rasterize_gaussians(*args)
+    if buffers is not None:
+        buffers.update(geom=geom, binning=binning, img=img)
     P = scene["means3D"].shape[0]
     st = backend.export_state(P, cam.image_width, cam.image_height, R, geom, binning, img)
     st = {k: v.cpu() for k, v in st.items()}

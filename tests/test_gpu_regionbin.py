@@ -160,19 +160,22 @@ def test_a_region_too_crowded_for_one_workgroup_falls_back_to_the_lsd_path(hip):
     assert (2000, W, H, False) not in hip._region_off and c["num_rendered"] > 0
 
 
-def test_fused_train_step_on_region_lists_is_the_lsd_run(hip):
+@pytest.mark.parametrize("P", [30000, 10000])
+def test_fused_train_step_on_region_lists_is_the_lsd_run(hip, P):
     """The deferred, depth-limited fused step (what bench.py times) on region-binned lists against the same trainer on
-    the LSD path: the run is the same run (bar of test_gpu_depth_limit.test_training_with_limits_is_the_same_run)."""
+    the LSD path: the run is the same run (bar of test_gpu_depth_limit.test_training_with_limits_is_the_same_run).
+    Every step's forward gets fresh buffers that usually held the previous camera's; P = 10 000 takes the one-workgroup
+    depth sort (csrc/gs_binning.hip) on the LSD path."""
     from test_gpu_depth_limit import make
     hip.binning = "lsd"
-    a = make(hip)
+    a = make(hip, P=P)
     a.depth_limit = "deferred"
     la = [a.step(k) for k in range(12)]
     a.sync()
     hip.binning = "region"
     hip._cam_cache.clear()
     hip._capacity_hint = hip._capacity_hint_limited = 0
-    b = make(hip)
+    b = make(hip, P=P)
     b.depth_limit = "deferred"
     used0, failed0 = hip.depth_limit_stats["used"], hip.depth_limit_stats["failed"]
     lb = [b.step(k) for k in range(12)]
