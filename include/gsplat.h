@@ -630,6 +630,20 @@ int gs_lgdwt_combine_p(const float* sums, const float* ssim_partials, int64_t n_
 int gs_lgdwt_combine_pp(const float* sums, const float* ssim_partials, int64_t n_partials, const float* dwt_partials,
                         int64_t n_dwt, const float* l1_partials, int64_t n_l1, float* running_mean,
                         const GsLgdwtParams* params /*host*/, float* out, void* stream);
+/* The criterion with the clamped image never written, for [C,H,W] images.  gs_lgdwt_fused_fwd = gs_l1_dwt2_patch_fwd_clamp_p
+ * (clamped_out not written; dwt_partials: gs_dwt_partials_count(C, H, W) rows of 12, the same bits) + gs_ssim_fwd_partials on
+ * clamp(raw, 0, 1) (ssim_partials: gs_ssim_partials_count(1, C, H, W); the same maps and partials bit for bit); add them up
+ * with gs_lgdwt_combine_pp.  gs_lgdwt_fused_bwd writes grad once, bit for bit what gs_l1_dwt2_patch_bwd (mask given; or
+ * gs_l1_dwt2_bwd with flags & 2; or gs_l1_bwd_dev) followed by gs_ssim_bwd_uniform accumulating onto it write, with
+ * img = flags & 1 ? clamp(raw, 0, 1) : raw; coef_dev = out[8..23] of the combine (c_l1, c_ssim, c_band x8, c_patch x3);
+ * flags & 4 zeroes the result where raw lies outside [0, 1] (clamp_src of gs_ssim_bwd_uniform).
+ * H, W (and ps) multiples of 4 and 16-byte aligned planes, else GS_E_UNSUPPORTED (use the separate calls). */
+int gs_lgdwt_fused_fwd(const float* raw, const float* gt, int32_t C, int32_t H, int32_t W, float C1, float C2, int32_t ps,
+                       const uint8_t* mask, float* dwt_partials, float* ssim_partials, float* dm_dmu1, float* dm_dsigma1_sq,
+                       float* dm_dsigma12, void* stream);
+int gs_lgdwt_fused_bwd(const float* raw, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, int32_t ps,
+                       const uint8_t* mask, const float* coef_dev, const float* dm_dmu1, const float* dm_dsigma1_sq,
+                       const float* dm_dsigma12, float* grad, void* stream);
 
 /* ---- optimiser (caller side of the path): fused Adam over ONE flat fp32 parameter buffer.
  * Replaces torch.optim.Adam(lr=0, eps=1e-15) with per-group learning rates,

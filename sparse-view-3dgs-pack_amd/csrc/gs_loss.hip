@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(GS_BLOCK) dwt2_l1_fwd_kernel(const float* __re
                                                                int C, int H, int W, float* band_sums, float* l1_sum,
                                                                float* __restrict__ clamped_out,
                                                                const uint8_t* __restrict__ patch_mask, int ps,
-                                                               float* patch_sums, float* __restrict__ partials) {
+                                                               float* patch_sums, float* __restrict__ partials, int clamp) {
   const int h1 = cdiv2(H), w1 = cdiv2(W), h2 = cdiv2(h1), w2 = cdiv2(w1);
   const int64_t total = (int64_t)C * h2 * w2;
   const int pnx = patch_mask ? W / ps : 0, pny = patch_mask ? H / ps : 0;
@@ -244,13 +244,14 @@ __global__ void __launch_bounds__(GS_BLOCK) dwt2_l1_fwd_kernel(const float* __re
     Px44 pa, pb;
     load_px44<FAST>(pred + (size_t)c * H * W, H, W, i2, j2, h1, w1, pa);
     load_px44<FAST>(gt + (size_t)c * H * W, H, W, i2, j2, h1, w1, pb);
-    if (FAST && clamped_out) {
+    if (FAST && (clamped_out || clamp)) {  // (clamp without clamped_out: the clamped image is not written)
 #pragma unroll
       for (int y = 0; y < 4; y++) {
 #pragma unroll
         for (int x = 0; x < 4; x++) pa.v[y][x] = fminf(fmaxf(pa.v[y][x], 0.f), 1.f);  // (torch.clamp: NaN stays NaN - v_max/v_min drop it; renders are finite)
-        reinterpret_cast<float4*>(clamped_out + (size_t)c * H * W + (size_t)(4 * i2 + y) * W)[j2] =
-            make_float4(pa.v[y][0], pa.v[y][1], pa.v[y][2], pa.v[y][3]);
+        if (clamped_out)
+          reinterpret_cast<float4*>(clamped_out + (size_t)c * H * W + (size_t)(4 * i2 + y) * W)[j2] =
+              make_float4(pa.v[y][0], pa.v[y][1], pa.v[y][2], pa.v[y][3]);
       }
     }
     Blk44 a, b;
@@ -622,19 +623,11 @@ __device__ __forceinline__ void ssim_conv_tile(const float (*tile)[SH][SH + 1], 
   }
 }
 
-__global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
-                                                            int H, int W, float C1, float C2, float* __restrict__ ssim_map,
-                                                            float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
-                                                            float* __restrict__ dm_dsigma12, float* sum_out, float* __restrict__ partials,
-                                                            int planes) {
-  constexpr int LDS_WORDS = (2 * SH * (SH + 1) > 5 * SH * HS) ? 2 * SH * (SH + 1) : 5 * SH * HS;
-  __shared__ float lds_buf[LDS_WORDS];
-  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
-  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
-  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
-  if (!tl.live) return;
-  const size_t plane = (size_t)tl.z * H * W;
-  const int bx = tl.bx, by = tl.by;
+// The pieces of ssim_fwd_kernel, shared with lgdwt_fwd_kernel (which must produce the same bits).
+__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }  // (as dwt2_l1_fwd_kernel clamps)
+// clamp1: img1 is staged as clamp(img1, 0, 1) (zero padding stays zero)
+__device__ __forceinline__ void ssim_stage_fwd(const float* __restrict__ img1, const float* __restrict__ img2, size_t plane,
+                                               int H, int W, int bx, int by, bool clamp1, float (*tile)[SH][SH + 1]) {
   // Halo tile loads.  Rows are 42 floats starting at column bx - 5: with W a multiple of 4 (and so every plane and row
   // 16-byte aligned) the aligned span [bx - 8, bx + 40) is fetched as 12 float4 per row - 2 vector loads per thread and
   // plane instead of 7 scalar ones (a float4 lies entirely inside or entirely outside the image); else element-wise.
@@ -663,7 +656,7 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restr
         for (int e = 0; e < 4; e++) {
           const int c = c0 + e;
           if (c >= 0 && c < SH) {
-            tile[0][r][c] = av[e];
+            tile[0][r][c] = clamp1 ? clamp01(av[e]) : av[e];
             tile[1][r][c] = bv[e];
           }
         }
@@ -688,14 +681,16 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restr
     for (int it = 0; it < NIT; it++) {
       const int k = threadIdx.x + it * GS_BLOCK;
       if (k < SH * SH) {
-        tile[0][k / SH][k % SH] = a[it];
+        tile[0][k / SH][k % SH] = clamp1 ? clamp01(a[it]) : a[it];
         tile[1][k / SH][k % SH] = b[it];
       }
     }
   }
-  __syncthreads();
-  float out[4][5];
-  ssim_conv_tile<5, true>(tile, hor, out);
+}
+// the per-pixel tail: SSIM map and the three derivative maps of this thread's 4 pixels; returns their SSIM sum
+__device__ __forceinline__ float ssim_fwd_pixels(const float (&out)[4][5], size_t plane, int H, int W, int bx, int by, float C1,
+                                                 float C2, float* __restrict__ ssim_map, float* __restrict__ dm_dmu1,
+                                                 float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12) {
   const int lx = threadIdx.x & 31, ly0 = threadIdx.x >> 5;
   float msum = 0.f;
 #pragma unroll
@@ -726,18 +721,42 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restr
       dm_dsigma12[o] = (2 * Cc) * inv_AB;
     }
   }
-  if (partials) {
-    // one plain store per workgroup; gs_lgdwt_combine_p adds them up.  (An atomic on ONE address per workgroup is
-    // serialised device-wide at ~14 ns each on this 8-XCD part: 6120 of them took 86 us of a 98-us kernel.)
-    __shared__ float red[GS_BLOCK / 64];
-    float x = msum;
+  return msum;
+}
+__device__ __forceinline__ void ssim_store_partial(float msum, float* __restrict__ partials, int linear) {
+  // one plain store per workgroup; gs_lgdwt_combine_p adds them up.  (An atomic on ONE address per workgroup is
+  // serialised device-wide at ~14 ns each on this 8-XCD part: 6120 of them took 86 us of a 98-us kernel.)
+  __shared__ float red[GS_BLOCK / 64];
+  float x = msum;
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0)
-      partials[tl.linear] = (red[0] + red[1]) + (red[2] + red[3]);
+  for (int off = 32; off >= 1; off >>= 1) x += __shfl_down(x, off, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    partials[linear] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                            int H, int W, float C1, float C2, float* __restrict__ ssim_map,
+                                                            float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
+                                                            float* __restrict__ dm_dsigma12, float* sum_out, float* __restrict__ partials,
+                                                            int planes) {
+  constexpr int LDS_WORDS = (2 * SH * (SH + 1) > 5 * SH * HS) ? 2 * SH * (SH + 1) : 5 * SH * HS;
+  __shared__ float lds_buf[LDS_WORDS];
+  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
+  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
+  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
+  if (!tl.live) return;
+  const size_t plane = (size_t)tl.z * H * W;
+  const int bx = tl.bx, by = tl.by;
+  ssim_stage_fwd(img1, img2, plane, H, W, bx, by, false, tile);
+  __syncthreads();
+  float out[4][5];
+  ssim_conv_tile<5, true>(tile, hor, out);
+  const float msum = ssim_fwd_pixels(out, plane, H, W, bx, by, C1, C2, ssim_map, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
+  if (partials) {
+    ssim_store_partial(msum, partials, tl.linear);
   } else if (sum_out) {  // uniform branch: mean SSIM without a second pass over the map
     float acc[1] = {msum};
     __syncthreads();
@@ -745,22 +764,10 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_kernel(const float* __restr
   }
 }
 
-__global__ void __launch_bounds__(GS_BLOCK) ssim_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
-                                                            int H, int W, const float* __restrict__ dL_dmap,
-                                                            const float* __restrict__ dm_dmu1,
-                                                            const float* __restrict__ dm_dsigma1_sq,
-                                                            const float* __restrict__ dm_dsigma12,
-                                                            float* __restrict__ dL_dimg1, const float* __restrict__ coef_dev,
-                                                            int accumulate, const float* __restrict__ clamp_src, int planes) {
-  constexpr int LDS_WORDS = (3 * SH * (SH + 1) > 3 * SH * HS) ? 3 * SH * (SH + 1) : 3 * SH * HS;
-  __shared__ float lds_buf[LDS_WORDS];
-  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
-  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
-  const float gu = coef_dev ? coef_dev[0] : 0.f;  // uniform dL/dssim_map (mean reduction upstream)
-  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
-  if (!tl.live) return;
-  const size_t plane = (size_t)tl.z * H * W;
-  const int bx = tl.bx, by = tl.by;
+// ssim_bwd_kernel's staging of dm_* x dL/dmap (dL_dmap NULL: the uniform gu) with the halo, shared with lgdwt_bwd_kernel
+__device__ __forceinline__ void ssim_stage_bwd(const float* __restrict__ dL_dmap, float gu, const float* __restrict__ dm_dmu1,
+                                               const float* __restrict__ dm_dsigma1_sq, const float* __restrict__ dm_dsigma12,
+                                               size_t plane, int H, int W, int bx, int by, float (*tile)[SH][SH + 1]) {
   const bool vec = (W & 3) == 0 && !dL_dmap &&
                    ((((uintptr_t)dm_dmu1) | ((uintptr_t)dm_dsigma1_sq) | ((uintptr_t)dm_dsigma12)) & 15) == 0;
   if (vec) {  // (see ssim_fwd_kernel; uniform upstream gradient only - the train step's case)
@@ -824,6 +831,25 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_bwd_kernel(const float* __restr
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(GS_BLOCK) ssim_bwd_kernel(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                            int H, int W, const float* __restrict__ dL_dmap,
+                                                            const float* __restrict__ dm_dmu1,
+                                                            const float* __restrict__ dm_dsigma1_sq,
+                                                            const float* __restrict__ dm_dsigma12,
+                                                            float* __restrict__ dL_dimg1, const float* __restrict__ coef_dev,
+                                                            int accumulate, const float* __restrict__ clamp_src, int planes) {
+  constexpr int LDS_WORDS = (3 * SH * (SH + 1) > 3 * SH * HS) ? 3 * SH * (SH + 1) : 3 * SH * HS;
+  __shared__ float lds_buf[LDS_WORDS];
+  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
+  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
+  const float gu = coef_dev ? coef_dev[0] : 0.f;  // uniform dL/dssim_map (mean reduction upstream)
+  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
+  if (!tl.live) return;
+  const size_t plane = (size_t)tl.z * H * W;
+  const int bx = tl.bx, by = tl.by;
+  ssim_stage_bwd(dL_dmap, gu, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, plane, H, W, bx, by, tile);
   __syncthreads();
   float out[4][3];
   ssim_conv_tile<3, false>(tile, hor, out);
@@ -844,6 +870,156 @@ __global__ void __launch_bounds__(GS_BLOCK) ssim_bwd_kernel(const float* __restr
     // gradient of clamp(x, 0, 1) folded in: zero where the un-clamped source was outside [0, 1]
     if (clamp_src && (r < 0.f || r > 1.f)) dL = 0.f;
     dL_dimg1[o] = dL;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ fused criterion passes
+// The criterion with the clamped image never written (gs_lgdwt_fused_fwd / _bwd).  Forward: dwt2_l1_fwd_kernel<true> clamps
+// as it loads and stores its rows of 12 sums (the grouping - and so the bits - of gs_l1_dwt2_patch_fwd_clamp_p), and
+// ssim_fwd_clamp_kernel is ssim_fwd_kernel on clamp(raw), clamped as the halo is staged: the same maps and partials bit for
+// bit.  Backward: one kernel for the SSIM, DWT, L1 and patch gradients (lgdwt_bwd_kernel below).
+#define LGDWT_CLAMP 1       // the criterion sees clamp(raw, 0, 1)
+#define LGDWT_DWT 2         // the band adjoint (else only L1, plus the patch term when a mask is given)
+#define LGDWT_CLAMP_MASK 4  // backward: zero the gradient where raw lies outside [0, 1]
+__global__ void __launch_bounds__(GS_BLOCK) ssim_fwd_clamp_kernel(const float* __restrict__ raw, const float* __restrict__ gt,
+                                                                  int H, int W, int planes, float C1, float C2,
+                                                                  float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
+                                                                  float* __restrict__ dm_dsigma12, float* __restrict__ partials) {
+  constexpr int LDS_WORDS = (2 * SH * (SH + 1) > 5 * SH * HS) ? 2 * SH * (SH + 1) : 5 * SH * HS;
+  __shared__ float lds_buf[LDS_WORDS];
+  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
+  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
+  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
+  if (!tl.live) return;
+  const size_t plane = (size_t)tl.z * H * W;
+  const int bx = tl.bx, by = tl.by;
+  ssim_stage_fwd(raw, gt, plane, H, W, bx, by, true, tile);
+  __syncthreads();
+  float out[4][5];
+  ssim_conv_tile<5, true>(tile, hor, out);
+  const float msum = ssim_fwd_pixels(out, plane, H, W, bx, by, C1, C2, nullptr, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
+  ssim_store_partial(msum, partials, tl.linear);
+}
+
+// What dwt2_l1_bwd_kernel<true> writes for this thread's 4 pixels (column c4 of a 4 x 4 block, its rows 0..3): a, b are the
+// column's criterion image and ground truth; the block's other columns are in lanes ^1, ^2, ^3.  Same operations on the same
+// values as there, so the same bits; every lane of the wave must take part (the exchanges read all of them).
+__device__ __forceinline__ void dwt2_l1_adjoint_col(const float (&a)[4], const float (&b)[4], int c4, const float (&cf)[8],
+                                                    float c1l, float (&g)[4]) {
+  float pa[4], pb[4];  // the column next to this one inside its level-1 blocks
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    pa[m] = __shfl_xor(a[m], 1, 64);
+    pb[m] = __shfl_xor(b[m], 1, 64);
+  }
+  const bool right = (c4 & 1) != 0, cc = (c4 & 2) != 0;
+  Bands A[2], B[2];  // level-1 blocks of rows (0, 1) and (2, 3)
+#pragma unroll
+  for (int r = 0; r < 2; r++) {
+    A[r] = haar_block(right ? pa[2 * r] : a[2 * r], right ? a[2 * r] : pa[2 * r], right ? pa[2 * r + 1] : a[2 * r + 1],
+                      right ? a[2 * r + 1] : pa[2 * r + 1]);
+    B[r] = haar_block(right ? pb[2 * r] : b[2 * r], right ? b[2 * r] : pb[2 * r], right ? pb[2 * r + 1] : b[2 * r + 1],
+                      right ? b[2 * r + 1] : pb[2 * r + 1]);
+  }
+  float la[2][2], lb[2][2];  // LL1 [r][column pair], the other pair's from lane ^2
+#pragma unroll
+  for (int r = 0; r < 2; r++) {
+    const float oa = __shfl_xor(A[r].ll, 2, 64), ob = __shfl_xor(B[r].ll, 2, 64);
+    la[r][0] = cc ? oa : A[r].ll;
+    la[r][1] = cc ? A[r].ll : oa;
+    lb[r][0] = cc ? ob : B[r].ll;
+    lb[r][1] = cc ? B[r].ll : ob;
+  }
+  const Bands a2 = haar_block(la[0][0], la[0][1], la[1][0], la[1][1]);
+  const Bands b2 = haar_block(lb[0][0], lb[0][1], lb[1][0], lb[1][1]);
+  float da, db, dc, dd;
+  haar_block_adj(cf[4] * sgnf(a2.ll - b2.ll), cf[5] * sgnf(a2.lh - b2.lh), cf[6] * sgnf(a2.hl - b2.hl),
+                 cf[7] * sgnf(a2.hh - b2.hh), da, db, dc, dd);
+#pragma unroll
+  for (int r = 0; r < 2; r++) {
+    const float dl = r == 0 ? (cc ? db : da) : (cc ? dd : dc);
+    float ea, eb, ec, ed;
+    haar_block_adj(cf[0] * sgnf(A[r].ll - B[r].ll) + dl, cf[1] * sgnf(A[r].lh - B[r].lh), cf[2] * sgnf(A[r].hl - B[r].hl),
+                   cf[3] * sgnf(A[r].hh - B[r].hh), ea, eb, ec, ed);
+    g[2 * r] = right ? eb : ea;
+    g[2 * r + 1] = right ? ed : ec;
+  }
+#pragma unroll
+  for (int m = 0; m < 4; m++) g[m] += c1l * sgnf(a[m] - b[m]);
+}
+
+// Backward: ssim_bwd_kernel (uniform dL/dmap = coef[1]) with the DWT / L1 / patch gradient of the same pixels added in the
+// order of the two-kernel sequence it replaces (dwt2_l1_bwd_kernel<true> writes g, ssim_bwd_kernel adds to it):
+// dL = ((out0 + a 2 out1) + gt out2) + g, then the clamp mask.  One write of the gradient, no read of it.
+// coef: out[8..23] of the combine - 0 c_l1, 1 c_ssim, 2..9 c_band, 10..12 c_patch.
+// (72 VGPRs with the hint, no scratch: 7 waves per SIMD, as ssim_bwd_kernel; 73 without it, one register over)
+__global__ void __launch_bounds__(GS_BLOCK) __attribute__((amdgpu_waves_per_eu(7))) lgdwt_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ gt, int H,
+                                                             int W, int planes, int flags, const uint8_t* __restrict__ patch_mask,
+                                                             int ps, const float* __restrict__ coef,
+                                                             const float* __restrict__ dm_dmu1,
+                                                             const float* __restrict__ dm_dsigma1_sq,
+                                                             const float* __restrict__ dm_dsigma12, float* __restrict__ grad) {
+  constexpr int LDS_WORDS = (3 * SH * (SH + 1) > 3 * SH * HS) ? 3 * SH * (SH + 1) : 3 * SH * HS;
+  __shared__ float lds_buf[LDS_WORDS];
+  float (*tile)[SH][SH + 1] = reinterpret_cast<float (*)[SH][SH + 1]>(lds_buf);
+  float (*hor)[SH][HS] = reinterpret_cast<float (*)[SH][HS]>(lds_buf);
+  const float gu = coef[1];
+  const SsimTile tl = ssim_tile_of_block((W + ST - 1) / ST, (H + ST - 1) / ST, planes);
+  if (!tl.live) return;
+  const size_t plane = (size_t)tl.z * H * W;
+  const int bx = tl.bx, by = tl.by;
+  // this thread's 4 output pixels (column lx, rows 4 ly0 .. + 3) and their DWT / L1 gradient g: formed before the
+  // convolution (their loads in flight with the halo's), so only r, b and g stay live across it
+  const int lx = threadIdx.x & 31, ly0 = threadIdx.x >> 5;
+  const int x = bx + lx, y0 = by + 4 * ly0;
+  const bool live = x < W && y0 < H;  // (H, W multiples of 4: whole 4 x 4 blocks, so whole lane quads, are live or not)
+  const bool clamp = (flags & LGDWT_CLAMP) != 0;
+  float r[4], b[4];
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    const size_t o = plane + (size_t)(y0 + m) * W + x;
+    r[m] = live ? raw[o] : 0.f;
+    b[m] = live ? gt[o] : 0.f;
+  }
+  ssim_stage_bwd(nullptr, gu, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, plane, H, W, bx, by, tile);
+  float g[4];
+  {
+    float a[4];
+#pragma unroll
+    for (int m = 0; m < 4; m++) a[m] = clamp ? clamp01(r[m]) : r[m];
+    const float c1l = coef[0];
+    if ((flags & LGDWT_DWT) || patch_mask) {  // (grid-uniform)
+      float cf[8];
+#pragma unroll
+      for (int k = 0; k < 8; k++) cf[k] = coef[2 + k];
+      if (patch_mask) {
+        const int py = y0 / ps, px = (x & ~3) / ps, pnx = W / ps, pny = H / ps;
+        if (live && py < pny && px < pnx && patch_mask[py * pnx + px] != 0) {
+          cf[1] += coef[10];
+          cf[2] += coef[11];
+          cf[3] += coef[12];
+        }
+      }
+      dwt2_l1_adjoint_col(a, b, lx & 3, cf, c1l, g);
+    } else {
+#pragma unroll
+      for (int m = 0; m < 4; m++) g[m] = c1l * sgnf(a[m] - b[m]);  // (l1_bwd_kernel)
+    }
+  }
+  __syncthreads();
+  float out[4][3];
+  ssim_conv_tile<3, false>(tile, hor, out);
+  if (!live) return;
+#pragma unroll
+  for (int m = 0; m < 4; m++) {
+    const float a = clamp ? clamp01(r[m]) : r[m];
+    float dL = 0.0f;
+    dL += out[m][0];
+    dL += a * 2.0f * out[m][1];
+    dL += b[m] * out[m][2];
+    dL += g[m];
+    if ((flags & LGDWT_CLAMP_MASK) && (r[m] < 0.f || r[m] > 1.f)) dL = 0.f;
+    grad[plane + (size_t)(y0 + m) * W + x] = dL;
   }
 }
 
@@ -928,19 +1104,19 @@ static inline unsigned dwt2_fwd_workgroups(int32_t C, int32_t H, int32_t W) {
 }
 static int dwt2_l1_fwd_launch(const float* pred, const float* gt, int32_t C, int32_t H, int32_t W, float* band_sums,
                               float* l1_sum, hipStream_t s, float* clamped_out = nullptr, const uint8_t* patch_mask = nullptr,
-                              int ps = 0, float* patch_sums = nullptr, float* partials = nullptr) {
+                              int ps = 0, float* patch_sums = nullptr, float* partials = nullptr, bool clamp = false) {
   const int h2 = ((H + 1) / 2 + 1) / 2, w2 = ((W + 1) / 2 + 1) / 2;
   // few, long-running workgroups: every workgroup ends in nine atomics on one cache line, and at 1500 workgroups
   // (1080p) their serialisation was 40 % of the kernel (25.9 us at a 4096 cap, 15.1 us at 512)
   const dim3 grid(nblocks((int64_t)C * h2 * w2, GS_BLOCK, 512));
   if (dwt2_fast(pred, gt, clamped_out, H, W))
     hipLaunchKernelGGL(dwt2_l1_fwd_kernel<true>, grid, dim3(GS_BLOCK), 0, s, pred, gt, C, H, W, band_sums, l1_sum, clamped_out,
-                       patch_mask, ps, patch_sums, partials);
-  else if (clamped_out || patch_mask || partials)
+                       patch_mask, ps, patch_sums, partials, (int)clamp);
+  else if (clamped_out || patch_mask || partials || clamp)
     return GS_E_UNSUPPORTED;  // (H, W multiples of 4 and 16-byte aligned planes only: clamp with torch otherwise)
   else
     hipLaunchKernelGGL(dwt2_l1_fwd_kernel<false>, grid, dim3(GS_BLOCK), 0, s, pred, gt, C, H, W, band_sums, l1_sum,
-                       (float*)nullptr, (const uint8_t*)nullptr, 0, (float*)nullptr, (float*)nullptr);
+                       (float*)nullptr, (const uint8_t*)nullptr, 0, (float*)nullptr, (float*)nullptr, 0);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
 }
@@ -1275,5 +1451,54 @@ int gs_lgdwt_combine_p(const float* sums, const float* ssim_partials, int64_t n_
 }
 int gs_lgdwt_combine(const float* sums, float* running_mean, const GsLgdwtParams* p, float* out, void* stream) {
   return gs_lgdwt_combine_p(sums, nullptr, 0, running_mean, p, out, stream);
+}
+
+static inline bool lgdwt_fused_ok(const void* a, const void* b, const void* c, const void* d, const void* e, int32_t C, int32_t H,
+                                  int32_t W) {
+  return (H % 4) == 0 && (W % 4) == 0 && C <= 65535 &&
+         ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0);
+}
+static inline int lgdwt_fused_args(int32_t C, int32_t H, int32_t W, int32_t ps, const uint8_t* mask) {
+  if (C <= 0 || H <= 0 || W <= 0 || ps < 0) return GS_E_SHAPE;
+  if ((ps > 0) != (mask != nullptr)) return GS_E_NULL;
+  if (ps > 0 && (H < ps || W < ps)) return GS_E_SHAPE;
+  if (ps % 4 != 0) return GS_E_UNSUPPORTED;
+  return GS_OK;
+}
+int gs_lgdwt_fused_fwd(const float* raw, const float* gt, int32_t C, int32_t H, int32_t W, float C1, float C2, int32_t ps,
+                       const uint8_t* mask, float* dwt_partials, float* ssim_partials, float* dm_dmu1, float* dm_dsigma1_sq,
+                       float* dm_dsigma12, void* stream) {
+  if (!raw || !gt || !dwt_partials || !ssim_partials || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12) return GS_E_NULL;
+  const int rc = lgdwt_fused_args(C, H, W, ps, mask);
+  if (rc != GS_OK) return rc;
+  if (!lgdwt_fused_ok(raw, gt, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, C, H, W)) return GS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  {
+    GS_PROF(ST_DWT2_FWD, s);
+    float dummy_target = 0.f;  // (never dereferenced with partials given)
+    const int r = dwt2_l1_fwd_launch(raw, gt, C, H, W, &dummy_target, &dummy_target, s, nullptr, mask, ps, &dummy_target,
+                                     dwt_partials, true);
+    if (r != GS_OK) return r;
+  }
+  GS_PROF(ST_SSIM_FWD, s);
+  hipLaunchKernelGGL(ssim_fwd_clamp_kernel, dim3(ssim_launch_blocks(W, H, C)), dim3(GS_BLOCK), 0, s, raw, gt, H, W, C, C1, C2,
+                     dm_dmu1, dm_dsigma1_sq, dm_dsigma12, ssim_partials);
+  GS_LAUNCH_CHECK(s, 0);
+  return GS_OK;
+}
+int gs_lgdwt_fused_bwd(const float* raw, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, int32_t ps,
+                       const uint8_t* mask, const float* coef_dev, const float* dm_dmu1, const float* dm_dsigma1_sq,
+                       const float* dm_dsigma12, float* grad, void* stream) {
+  if (!raw || !gt || !coef_dev || !dm_dmu1 || !dm_dsigma1_sq || !dm_dsigma12 || !grad) return GS_E_NULL;
+  const int rc = lgdwt_fused_args(C, H, W, ps, mask);
+  if (rc != GS_OK) return rc;
+  if (!lgdwt_fused_ok(raw, gt, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, C, H, W) || ((uintptr_t)grad & 15) != 0)
+    return GS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  GS_PROF(ST_SSIM_BWD, s);
+  hipLaunchKernelGGL(lgdwt_bwd_kernel, dim3(ssim_launch_blocks(W, H, C)), dim3(GS_BLOCK), 0, s, raw, gt, H, W, C, flags, mask, ps,
+                     coef_dev, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, grad);
+  GS_LAUNCH_CHECK(s, 0);
+  return GS_OK;
 }
 }

@@ -188,6 +188,8 @@ PROTOTYPES = {
     "lgdwt_combine_p": (C.c_int, [_P, _P, _I64, _P, C.POINTER(GsLgdwtParams), _P, _P]),
     "ssim_partials_count": (C.c_int64, [_I32, _I32, _I32, _I32]),
     "ssim_fwd_partials": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _P, _P, _P, _P]),
+    "lgdwt_fused_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _F, _F, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "lgdwt_fused_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "adam_step": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P]),
     "adam_step_gated": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P, _P]),
     "adam_step_masked": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P, _P, _P]),
@@ -215,7 +217,9 @@ PROTOTYPES = {
 DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_uninstanced", "export_tile_order", "export_tile_stop_depth", "forward_status", "forward_bin", "export_binning_region", "debug_blend_stats", "adam_step_gated", "tile_depth_limit_floats", "profile_enable", "profile_only", "profile_reset", "profile_stage_count", "profile_stage_name", "profile_read",
                "forward_render_x", "backward_x", "forward_tile_order",
                # the image stage (exposure, clamp, alpha mask) and the exposures' Adam: the oracle restates them in torch
-               "image_stage_partials_count", "image_stage_fwd", "image_stage_bwd", "exposure_adam")
+               "image_stage_partials_count", "image_stage_fwd", "image_stage_bwd", "exposure_adam",
+               # the criterion without its clamped image: a fusion of kernels the checker has, compared against them on the GPU
+               "lgdwt_fused_fwd", "lgdwt_fused_bwd")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

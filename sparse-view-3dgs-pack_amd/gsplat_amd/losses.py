@@ -12,6 +12,10 @@ import torch
 
 BANDS = ("LL1", "LH1", "HL1", "HH1", "LL2", "LH2", "HL2", "HH2")
 
+# FusedLGDWTLoss writes the image gradient with ONE kernel and forms no clamped image (gs_lgdwt_fused_fwd / _bwd) where the
+# library has them and the shape allows (_FusedParams.fused_shape) - the same bits; False: the kernel sequence they replace.
+FUSED_PASSES = True
+
 
 def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
@@ -319,7 +323,22 @@ class FusedLGDWTLoss(torch.autograd.Function):
         # every gradient depended in the last bits on which workgroup finished first
         dwt_part = l1_part = None
         fast = H % 4 == 0 and W % 4 == 0
-        if patch_folded or (params.dwt_enable and fast and params.clamp):
+        # The gradient as ONE kernel (gs_lgdwt_fused_bwd) wherever it writes the bits of the kernels below - every case but the
+        # separate patch kernels; and then, where the sums come from gs_l1_dwt2_patch_fwd_clamp_p, the clamped image is not
+        # written at all: that kernel and the SSIM forward each clamp as they load (gs_lgdwt_fused_fwd, the same bits)
+        fused = bool(FUSED_PASSES and params.fused_shape and hasattr(api, "_lgdwt_fused_bwd")
+                     and (patch_folded or not params.patch_enable) and raw.data_ptr() % 16 == 0 and gt.data_ptr() % 16 == 0)
+        ctx.fused = fused
+        ctx.fused_flags = ((1 if params.clamp or patch_folded else 0) | (2 if params.dwt_enable else 0)
+                           | (4 if params.clamp and stage is None else 0))
+        partials = torch.empty((params.n_ssim_partials,), dtype=torch.float32, device=raw.device)
+        if fused and (patch_folded or (params.dwt_enable and params.clamp)):
+            img = None
+            dwt_part = torch.empty((params.n_dwt_partials * 12,), dtype=torch.float32, device=raw.device)
+            api.call("lgdwt_fused_fwd", raw.data_ptr(), gt.data_ptr(), Cc, H, W, 0.01 ** 2, 0.03 ** 2,
+                     ctx_ps(params) if patch_folded else 0, mask.data_ptr() if patch_folded else None, dwt_part.data_ptr(),
+                     partials.data_ptr(), d1.data_ptr(), d2.data_ptr(), d3.data_ptr(), st)
+        elif patch_folded or (params.dwt_enable and fast and params.clamp):
             img = torch.empty_like(raw)
             dwt_part = torch.empty((params.n_dwt_partials * 12,), dtype=torch.float32, device=raw.device)
             api.call("l1_dwt2_patch_fwd_clamp_p", raw.data_ptr(), gt.data_ptr(), Cc, H, W, ctx_ps(params) if patch_folded else 0,
@@ -334,10 +353,9 @@ class FusedLGDWTLoss(torch.autograd.Function):
                 api.call("l1_fwd_p", img.data_ptr(), gt.data_ptr(), img.numel(), l1_part.data_ptr(), st)
             else:
                 api.call("l1_fwd", img.data_ptr(), gt.data_ptr(), img.numel(), sums.data_ptr(), st)
-        # SSIM sum as per-workgroup partials (no atomics; lgdwt_combine_p adds them up in a fixed order)
-        partials = torch.empty((params.n_ssim_partials,), dtype=torch.float32, device=raw.device)
-        api.call("ssim_fwd_partials", img.data_ptr(), gt.data_ptr(), 1, Cc, H, W, 0.01 ** 2, 0.03 ** 2,
-                 partials.data_ptr(), d1.data_ptr(), d2.data_ptr(), d3.data_ptr(), st)
+        if img is not None:   # SSIM sum as per-workgroup partials (no atomics; lgdwt_combine_p adds them up in a fixed order)
+            api.call("ssim_fwd_partials", img.data_ptr(), gt.data_ptr(), 1, Cc, H, W, 0.01 ** 2, 0.03 ** 2,
+                     partials.data_ptr(), d1.data_ptr(), d2.data_ptr(), d3.data_ptr(), st)
         if params.patch_enable and not patch_folded:
             api.call("patch_dwt_fwd", img.data_ptr(), gt.data_ptr(), Cc, H, W, ctx_ps(params), mask.data_ptr(),
                      sums[10:].data_ptr(), st)
@@ -365,6 +383,15 @@ class FusedLGDWTLoss(torch.autograd.Function):
         unit = ctx.ops._unit.get(g.device)
         coef = out[8:24] if (unit is not None and g.data_ptr() == unit.data_ptr()) else (out[8:24] * g).contiguous()
         grad = torch.empty_like(raw)
+        if getattr(ctx, "fused", False):
+            hook = getattr(ctx.ops, "before_last_backward_kernel", None)
+            if hook is not None:
+                hook()
+            ps = ctx_ps(params) if params.patch_enable else 0
+            api.call("lgdwt_fused_bwd", raw.data_ptr(), gt.data_ptr(), Cc, H, W, ctx.fused_flags, ps,
+                     mask.data_ptr() if ps else None, coef.data_ptr(), d1.data_ptr(), d2.data_ptr(), d3.data_ptr(),
+                     grad.data_ptr(), st)
+            return None, _image_stage_bwd(api, getattr(ctx, "stage", None), grad, H, W, st), None, None, None, None, None, None
         if ctx.patch_folded:
             api.call("l1_dwt2_patch_bwd", img.data_ptr(), gt.data_ptr(), Cc, H, W, ctx_ps(params), mask.data_ptr(),
                      coef.data_ptr(), coef[2:].data_ptr(), coef[10:].data_ptr(), grad.data_ptr(), 0, st)
@@ -383,15 +410,21 @@ class FusedLGDWTLoss(torch.autograd.Function):
         api.call("ssim_bwd_uniform", img.data_ptr(), gt.data_ptr(), 1, Cc, H, W, coef[1:].data_ptr(), d1.data_ptr(),
                  d2.data_ptr(), d3.data_ptr(), grad.data_ptr(), 1,
                  raw.data_ptr() if params.clamp and stage is None else None, st)
-        if stage is not None:   # (the clamp's gradient is folded in here, with the mask and the exposure)
-            g_raw = torch.empty_like(grad)
-            api.call("image_stage_bwd", stage.raw.data_ptr(), _p(stage.exposure), _p(stage.alpha), grad.data_ptr(), H, W,
-                     g_raw.data_ptr(), _p(stage.partials), st)
-            if stage.exposure_grad is not None:
-                api.call("exposure_adam", stage.partials.data_ptr(), stage.partials.numel() // 12, 0,
-                         stage.exposure_grad.data_ptr(), None, None, None, 1, 0.0, 0.0, 0.0, 0.0, 0, None, st)
-            grad = g_raw
-        return None, grad, None, None, None, None, None, None
+        return None, _image_stage_bwd(api, stage, grad, H, W, st), None, None, None, None, None, None
+
+
+def _image_stage_bwd(api, stage, grad, H, W, st):
+    """The criterion's image gradient through the image stage, if there is one (the clamp's gradient is folded in there,
+    with the mask and the exposure)."""
+    if stage is None:
+        return grad
+    g_raw = torch.empty_like(grad)
+    api.call("image_stage_bwd", stage.raw.data_ptr(), _p(stage.exposure), _p(stage.alpha), grad.data_ptr(), H, W,
+             g_raw.data_ptr(), _p(stage.partials), st)
+    if stage.exposure_grad is not None:
+        api.call("exposure_adam", stage.partials.data_ptr(), stage.partials.numel() // 12, 0,
+                 stage.exposure_grad.data_ptr(), None, None, None, 1, 0.0, 0.0, 0.0, 0.0, 0, None, st)
+    return g_raw
 
 
 def ctx_ps(params):
@@ -453,6 +486,9 @@ class _FusedParams:
         self.n_ssim_partials = int(crit.ops.api.raw("ssim_partials_count")(1, Cc, H, W))
         self.n_dwt_partials = int(crit.ops.api.raw("dwt_partials_count")(Cc, H, W))
         self.n_l1_partials = int(crit.ops.api.raw("l1_partials_count")(Cc * H * W))
+        # gs_lgdwt_fused_fwd / _bwd take whole 4 x 4 DWT blocks (and patches of them)
+        self.fused_shape = bool(H % 4 == 0 and W % 4 == 0 and Cc <= 65535
+                                and (not self.patch_enable or self.patch_size % 4 == 0))
 
 
 class LGDWTCriterion:
