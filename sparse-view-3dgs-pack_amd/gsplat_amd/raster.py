@@ -34,6 +34,28 @@ def _prep(t, device):
     return t.contiguous()
 
 
+def _regions(W, H):
+    """Regions of a W x H view: blocks of 4 x 4 tiles of 16 x 16 pixels (csrc/gs_common.h RG_TILES)."""
+    return ((((W + 15) // 16) + 3) // 4) * ((((H + 15) // 16) + 3) // 4)
+
+
+class _Forward:
+    """What the steps of one forward (RasterBackend._rasterize_gaussians) share: its view, Gaussians, buffers, outputs and
+    camera state; on the GPU also its stream and pinned status block."""
+    __slots__ = ("device", "stream", "view", "g", "P", "W", "H", "geom", "img", "empty", "radii", "out_color", "out_invdepth",
+                 "out_extra", "fsgs", "extra", "cache", "use_order", "use_limit", "static", "cur", "status")
+
+    def __init__(self, device, stream, view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs, extra,
+                 cache, use_order, use_limit, static):
+        self.device, self.stream, self.view, self.g = device, stream, view, g
+        self.P, self.W, self.H = P, W, H
+        self.geom, self.img, self.empty, self.radii = geom, img, torch.empty((0,), dtype=torch.uint8, device=device), radii
+        self.out_color, self.out_invdepth, self.out_extra = out_color, out_invdepth, out_extra
+        self.fsgs, self.extra = fsgs, extra
+        self.cache, self.use_order, self.use_limit, self.static = cache, use_order, use_limit, static
+        self.cur = self.status = None
+
+
 class RasterBackend:
     """Binds one implementation of the C ABI (`api`) to one torch device type."""
 
@@ -69,7 +91,6 @@ class RasterBackend:
         # one-shot, set with camera_key by GaussianRasterizer: the caller named the camera and did not decline depth limits
         # (GaussianRasterizer.camera_limits) - the forward may use this camera's verified limits as with GS_DEPTH_LIMIT=1
         self.camera_key_limits = False
-        self._region_key = None    # (P, W, H, limited) of the forward being served (see _region_off); None in the backward
         self._vm_ids = {}
         self.camera_cache_stats = dict(hits=0, misses=0, hashed=0)
         self.order_hint_on = True   # (False: image order - outputs do not depend on it, see GsScratch.tile_order_hint)
@@ -103,6 +124,7 @@ class RasterBackend:
         self._side_streams = {}
         self._rows_ws = {}        # (device, bytes) -> [persistent gradient-row workspace of the fused step, rows all zero?]
         self.rows_epoch = 0       # bumped whenever a fused backward found (or may have left) that workspace dirty
+        self._built = None        # the GsView / GsGaussians of the last forward (see _structs)
         self._early = None        # what launch_uninstanced_early needs of the last forward
         self.two_phase_launches = 0
         self._uninst_done = None
@@ -131,8 +153,17 @@ class RasterBackend:
                 "gsplat %s backend got a tensor on %s - the rasterizer has no fallback path"
                 % (self.device_type, t.device))
 
+    def _tile_cull(self, device):
+        """GsView.tile_cull of this backend's views: 0 = the reference's lists, 1 = culled lists built by the LSD path,
+        2 = by region binning.  (A forward may still take the LSD path for its own lists, see _rasterize_gaussians; the
+        backward only asks whether they were culled.)"""
+        cull = int(self.tile_cull)
+        if cull and self.binning in ("region", "auto") and device.type == "cuda":
+            return 2
+        return cull
+
     def _view(self, keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
-              degree, prefiltered, antialiasing, debug):
+              degree, prefiltered, antialiasing, debug, tile_cull=None):
         v = GsView()
         v.image_height, v.image_width = int(H), int(W)
         v.tanfovx, v.tanfovy = float(tanfovx), float(tanfovy)
@@ -141,10 +172,7 @@ class RasterBackend:
         v.prefiltered, v.antialiasing, v.debug = int(bool(prefiltered)), int(bool(antialiasing)), int(bool(debug))
         if self.force_rowwise_entries:   # (test hook: GsView.debug bit 1, csrc/gs_tilebin.hip)
             v.debug |= 2
-        v.tile_cull = int(self.tile_cull)
-        if self.tile_cull and self.binning in ("region", "auto") and device.type == "cuda" and \
-                (self._region_key is None or self._region_key not in self._region_off):
-            v.tile_cull = 2
+        v.tile_cull = self._tile_cull(device) if tile_cull is None else tile_cull
         bg, viewmatrix, projmatrix, campos = (_prep(x, device) for x in (bg, viewmatrix, projmatrix, campos))
         keep += [bg, viewmatrix, projmatrix, campos]
         v.bg, v.viewmatrix, v.projmatrix, v.campos = _ptr(bg), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos)
@@ -228,7 +256,8 @@ class RasterBackend:
     def take_deferred(self):
         """The pending verdict of the last forward run with depth_limit_request = "defer", or None.  -> callable that
         waits for that forward and returns True when its limits held (outputs valid) - on False it has already
-        invalidated the camera's limits, and the caller must discard everything computed from that forward."""
+        invalidated the camera's limits, and the caller must discard everything computed from that forward.
+        (Only depth-limited forwards defer their verdict: see _forward_lists for the record.)"""
         d, self.deferred = self.deferred, None
         if d is None:
             return None
@@ -237,20 +266,21 @@ class RasterBackend:
             d["event"].synchronize()
             st = tuple(int(x) for x in d["status"][:4])
             ok = st[1] == 0 and st[2] == 0
-            if "regions" in d:
+            regions = d["regions"]
+            if regions:
                 # region binning learns the instance count only here: keep the capacity hint current, and tell a capacity
                 # overflow (render again with more room, the limits were fine) from limits that proved too tight
                 if st[3] > self.REGION_MAX_ENTRIES:
-                    self._region_off.add(d.get("size"))
-                self._update_hint(max(st[0], st[3] * d["regions"]), limited=d.get("limited", False))
+                    self._region_off.add(d["size"])
+                self._update_hint(max(st[0], st[3] * regions), limited=True)
                 self.last_deferred_num_rendered = st[0]
             if not ok:
                 self.depth_limit_stats["failed"] += 1
-                if st[2] != 0 or "regions" not in d:
+                if st[2] != 0 or not regions:
                     d["cache"]["limit_ok"] = False
                 if st[2] != 0:
                     self.limits_failed(d["cache"])
-            elif d.get("limited", False):
+            else:
                 self.limits_held(d["cache"])
             return ok
         return verdict
@@ -419,12 +449,6 @@ class RasterBackend:
     # written into the pinned host block by the forward's own last kernel (GsScratch.status_host) instead of by a copy
     # command behind it - one launch less on the stream.  False: gs_forward_status as before.
     STATUS_IN_RENDER = True
-    # Train step (a fused step is armed): the forward's last kernel (tile_order: the backward's launch order, the camera's next
-    # hints and depth bounds, the status block) is issued on the SIDE stream - nothing before the backward blend needs it, so
-    # it runs beside the criterion's first kernel instead of in front of it (GsScratch.defer_tile_order +
-    # gs_forward_tile_order); the backward waits for it.  False: in line, as the plain forward does.
-    SPLIT_TILE_ORDER = True
-    REUSE_BUILT = True   # the forward's GsView / GsGaussians structs serve its backward too
 
     def _side_stream(self, device):
         side = self._side_streams.get(device.index)
@@ -433,17 +457,6 @@ class RasterBackend:
         return side
     TWO_PHASE = os.environ.get("GS_TWO_PHASE_STEP", "1") != "0"
     TWO_PHASE_MIN_P = 100_000
-
-    # Where the side launch of the two-phase step (gs_step_uninstanced) is issued:
-    #   "loss_backward"  by the train step, right before the criterion's backward kernels (Trainer calls
-    #                    launch_uninstanced_early): it then runs under ssim_bwd / dwt2_l1_bwd and the backward blend
-    #   "ssim_backward"  from inside the criterion's backward, before its last kernel (ssim_bwd)
-    #   "raster_backward" at the start of the rasterizer's backward, next to the blend only (round 3)
-    # Same box, C3 (gpurun_out/r04/ab4.log): ssim_backward 0.983 ms/step (ssim_bwd 43 -> 52 us beside the stream, blend 0.40),
-    # loss_backward 1.024 (the stream starts 20 us earlier, under dwt2_l1_bwd too, and ssim_bwd takes 103 us beside it),
-    # raster_backward 1.012 replayed / 1.15 eager (no head start: the blend's 8 160 one-wave workgroups are dealt out first
-    # and the stream's workgroups trickle in behind them, phase 2 waits 0.17 ms for it).
-    UNINST_AT = "ssim_backward"
 
     def rasterize_gaussians(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
                              cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
@@ -457,13 +470,12 @@ class RasterBackend:
                                         extra_gain=extra_gain)
         self._early = None
         step = self.fused_step
-        if step is not None and not fsgs and means3D.device.type == "cuda" and self.UNINST_AT != "raster_backward":
+        if step is not None and not fsgs and means3D.device.type == "cuda":
             P = int(means3D.shape[0])
             if self.TWO_PHASE and P >= self.TWO_PHASE_MIN_P and not step.grad_out[0] and not step.rows_override:
                 self._early = dict(args=(bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
                                          projmatrix, campos, tanfovx, tanfovy, int(image_height), int(image_width),
-                                         scale_modifier, degree, antialiasing, debug),
-                                   extra=extra, extra_gain=extra_gain,
+                                         scale_modifier, degree, antialiasing, debug, extra, extra_gain),
                                    raw=raw, radii=out[2], geom=out[3], img=out[5], step=step, done=None)
         return out
 
@@ -474,24 +486,29 @@ class RasterBackend:
         e = self._early
         if e is None or e["done"] is not None:
             return False
-        (bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx,
-         tanfovy, H, W, scale_modifier, degree, antialiasing, debug) = e["args"]
-        device = means3D.device
-        self._region_key = None
-        built = getattr(self, "_built", None)
-        if self.REUSE_BUILT and built is not None and built["geom"] == e["geom"].data_ptr() and built["raw"] == e["raw"]:
-            view, g, keep = built["view"], built["g"], built["keep"]
-        else:
-            keep = []
-            view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
-                              False, antialiasing, debug)
-            g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, e["extra"],
-                            raw=e["raw"], extra_gain=e["extra_gain"])
+        view, g, keep = self._structs(e["geom"], e["raw"], *e["args"])
+        device = e["geom"].device
         empty = torch.empty((0,), dtype=torch.uint8, device=device)
         s = self._scratch(e["geom"], e["img"], empty, 0)
         e["done"] = self._launch_uninstanced(device, view, g, e["radii"], s, e["step"])
         e["keep"] = keep
         return True
+
+    def _structs(self, geom, raw, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
+                 projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree, antialiasing, debug, extra, extra_gain,
+                 sh_rest=None):
+        """-> (GsView, GsGaussians, tensors they point into) of the view and Gaussians the forward that wrote `geom` served:
+        the structs that forward built (same pointers; the train step's side launch and its backward), else built again."""
+        built = self._built
+        if built is not None and built["geom"] == geom.data_ptr() and built["raw"] == raw:
+            return built["view"], built["g"], built["keep"]
+        keep = []
+        device = means3D.device
+        view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
+                          False, antialiasing, debug)
+        g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra, raw=raw,
+                        extra_gain=extra_gain, sh_rest=sh_rest)
+        return view, g, keep
 
     def _launch_uninstanced(self, device, view, g, radii, s, step):
         main = torch.cuda.current_stream(device)
@@ -524,7 +541,6 @@ class RasterBackend:
         self._check_device(means3D)
         device = means3D.device
         P, H, W = int(means3D.shape[0]), int(image_height), int(image_width)
-        self._region_key = (P, W, H)
         f32 = dict(dtype=torch.float32, device=device)
         u8 = dict(dtype=torch.uint8, device=device)
         # every pixel and every radius is written by the kernels (gs_forward_geometry / gs_forward_render): empty, not
@@ -553,289 +569,254 @@ class RasterBackend:
             self._join_tile_order(device)   # (a forward whose backward never ran: its hints must be complete before this one reads them)
         cache = self._camera_cache(device, W, H, viewmatrix)
         static = self.static_capacity is not None
-        use_order = cache is not None and self.order_hint_on
         request, self.depth_limit_request = self.depth_limit_request, None
         keyed_limits, self.camera_key_limits = self.camera_key_limits and self.KEYED_LIMITS, False
         self.deferred = None
         use_limit = cache is not None and (self.depth_limit_on or request is not None or keyed_limits) and self.tile_cull
-        defer = request == "defer"
         # capture-safe mode always passes the limit buffer (+inf = no limit): the pointer is frozen into the graph
         limit = cache["limit"] if use_limit and (static or cache["limit_ok"]) else None
 
-        def scratch_of(binning, capacity, limit):
-            s = self._scratch(geom, img, binning, capacity)
-            if limit is not None:
-                s.tile_depth_limit = limit.data_ptr()
-            if static and self.static_step_tag is not None:
-                s.step_tag = self.static_step_tag.data_ptr()
-            return s
-
-        def render(scratch):
-            if use_order and cache["order_ok"]:
-                scratch.tile_order_hint = cache["order"].data_ptr()
-            # what this view measures becomes the hint of this camera's next visit: written by the forward's last launch
-            # straight into the camera's buffers (they are read - as this view's hints - before they are written)
-            if use_order:
-                scratch.tile_order_out = cache["order"].data_ptr()
-            if use_limit:
-                scratch.tile_depth_limit_out = cache["limit"].data_ptr()
-                scratch.tile_depth_limit_slack = cache["slack"].data_ptr()
-            self._render(scratch, fsgs, extra, view, g, out_color, out_invdepth, out_extra, stream)
-
-        def remember(scratch):
-            if use_order:
-                cache["order_ok"] = True
-            if use_limit:
-                cache["limit_ok"] = True
-
+        tile_cull = self._tile_cull(device)
+        # region binning, except for a size whose regions overfilled (_region_off) and, with binning = "auto", for long
+        # un-limited lists.  (Depth-limited lists are several times shorter: a size whose FULL lists overfill a region still
+        # bins its limited views by region - C2: 0.146 -> 0.04 ms of binning per step.)
+        if tile_cull == 2 and ((P, W, H, limit is not None) in self._region_off or (
+                self.binning == "auto" and limit is None and not static
+                and self._capacity_hint > self.REGION_AUTO_MAX * _regions(W, H))):
+            tile_cull = 1
         keep = []
-        # (depth-limited lists are several times shorter: a size whose FULL lists overfill a region still bins its limited
-        #  views by region - C2: 0.146 -> 0.04 ms of binning per step)
-        self._region_key = (P, W, H, limit is not None)
         view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
-                          degree, prefiltered, antialiasing, debug)
+                          degree, prefiltered, antialiasing, debug, tile_cull=tile_cull)
         g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra, raw=raw,
                         extra_gain=extra_gain, sh_rest=sh_rest)
-        stream = self._stream(device)
 
         gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
-        fill = self.scratch_fill
         geom = torch.empty((gb,), **u8)
         self._raw_geom = geom.data_ptr() if raw else None
         img = torch.empty((ib,), **u8)
-        if fill is not None:
-            fill("geom", geom)
-            fill("img", img)
-        empty = torch.empty((0,), **u8)
+        if self.scratch_fill is not None:
+            self.scratch_fill("geom", geom)
+            self.scratch_fill("img", img)
         # (the train step's side launch and its backward describe the same view and the same Gaussians: they take these
         #  structs - and the tensors `keep` holds alive - instead of building them again; keyed by this forward's geometry buffer)
         self._built = dict(geom=geom.data_ptr(), view=view, g=g, keep=keep, raw=raw)
         self._last_geom = (geom, P)   # (export_row_mask: the data-parallel step's early mask exchange)
-
-        def new_binning(cap):
-            _, _, bb, _ = self.scratch_bytes(P, W, H, cap)
-            binning = torch.empty((bb,), **u8)
-            if fill is not None:
-                fill("binning", binning)
-            self._remember_capacity(binning, cap)
-            return binning
+        f = _Forward(device, self._stream(device), view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs,
+                     extra, cache, cache is not None and self.order_hint_on, use_limit, static)
 
         if device.type != "cuda":
             nr = (C.c_int32 * 1)()
-            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(scratch_of(empty, 0, None)),
-                          radii.data_ptr(), C.cast(nr, C.c_void_p), stream)
+            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(self._scratch_of(f, f.empty, 0, None)),
+                          radii.data_ptr(), C.cast(nr, C.c_void_p), f.stream)
             num_rendered = int(nr[0])
-            binning = new_binning(num_rendered)
-            render(scratch_of(binning, num_rendered, None))
+            binning = self._new_binning(f, num_rendered)
+            self._render(f, self._scratch_of(f, binning, num_rendered, None))
             return (num_rendered, out_color, radii, geom, binning, img, out_invdepth) + tail
 
         # one pinned status block per device AND stream: two forwards in flight on different streams must not share it
         # (capture-safe mode: one per device, created before the capture - pinned memory cannot be allocated inside).
         # Words: num_rendered, overflow, trunc_failed, 0 (gs_forward_status; gs_forward_geometry writes word 0 alone)
-        cur = torch.cuda.current_stream(device)
-        pkey = (device.index, "static" if static else cur.cuda_stream)
+        f.cur = torch.cuda.current_stream(device)
+        pkey = (device.index, "static" if static else f.cur.cuda_stream)
         status = self._pinned_by_device.get(pkey)
         if status is None:
             status = self._pinned_by_device[pkey] = torch.zeros((16,), dtype=torch.int32).pin_memory()
-        self._pinned = status  # (last used: read by bench.py for the instance count of the last view)
-
-        def geometry(limit):
-            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(scratch_of(empty, 0, limit)),
-                          radii.data_ptr(), status.data_ptr(), stream)
-
-        if view.tile_cull == 2 and self.binning == "auto" and limit is None and not static:
-            regions = ((((W + 15) // 16) + 3) // 4) * ((((H + 15) // 16) + 3) // 4)
-            if self._capacity_hint > self.REGION_AUTO_MAX * regions:
-                view.tile_cull = 1   # long un-limited lists: the LSD path (same lists)
-        if view.tile_cull == 2:
-            out = self._forward_region(P, W, H, cache, limit, defer, static, status, cur, geom, img, view, g, radii, stream,
-                                       new_binning, scratch_of, render, remember)
-            if out is not None:
-                num_rendered, binning = out
-                return (num_rendered, out_color, radii, geom, binning, img, out_invdepth) + tail
-            # a region holds more Gaussians than one workgroup sorts: this size goes through the LSD path from now on
-            view.tile_cull = 1
-
-        if static:
-            # capture-safe: fixed capacity, no host wait, no re-run; the caller reads last_status() after the stream drained
-            cap = int(self.static_capacity)
-            geometry(limit)
-            binning = new_binning(cap)
-            s = scratch_of(binning, cap, limit)
-            render(s)
-            if limit is not None:
-                self.depth_limit_stats["used"] += 1  # (at capture time only: replays do not pass here)
-            self.api.call("forward_status", C.byref(s), status.data_ptr(), stream)
-            remember(s)
-            return (cap, out_color, radii, geom, binning, img, out_invdepth) + tail
-
-        for limit in ((limit, None) if limit is not None else (None,)):
-            geometry(limit)
-            cap = self._capacity_hint if self.optimistic else 0
-            if cap > 0 and limit is not None and self._capacity_hint_limited > 0:
-                cap = self._capacity_hint_limited
-            binning = None
-            if cap > 0:
-                # Optimistic path: the reference blocks the host on a D2H copy of num_rendered before it can
-                # size the binning buffer (rasterizer_impl.cu:284-288) and the GPU idles meanwhile.  Here the
-                # binning/blend phase is enqueued at once with a capacity predicted from the previous calls
-                # (the kernels read num_rendered on the device); the host then waits only for the geometry
-                # phase - the GPU is already sorting and blending - and re-runs the phase in the rare case
-                # the prediction was too small.
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                binning = new_binning(cap)
-                s = scratch_of(binning, cap, limit)
-                render(s)
-                ev.synchronize()
-            else:
-                cur.synchronize()  # the reference's blocking D2H (rasterizer_impl.cu:284)
-            num_rendered = int(status[0])
-            self._update_hint(num_rendered, limited=limit is not None)
-            if binning is None or num_rendered > cap:
-                binning = new_binning(num_rendered)
-                s = scratch_of(binning, num_rendered, limit)
-                render(s)
-            if limit is not None:
-                # depth-limited lists: the blend has checked that every bounded tile saturated inside the part of its
-                # list that is certainly complete; the host has to know before it hands the image out (this wait ends
-                # when the blend does, the un-limited path's when the geometry phase does)
-                self.depth_limit_stats["used"] += 1
-                if defer:
-                    # the caller collects the verdict later (take_deferred): its own status block, from a small ring -
-                    # a block is re-used only after eight further deferred forwards
-                    ring = self._status_ring.setdefault(device.index, [[], 0])
-                    if len(ring[0]) < 8:
-                        ring[0].append(torch.zeros((16,), dtype=torch.int32).pin_memory())
-                    block = ring[0][ring[1] % len(ring[0])]
-                    ring[1] += 1
-                    self.api.call("forward_status", C.byref(s), block.data_ptr(), stream)
-                    done = torch.cuda.Event()
-                    done.record(cur)
-                    self.deferred = dict(status=block, event=done, cache=cache, limited=True)
-                    remember(s)
-                    return (num_rendered, out_color, radii, geom, binning, img, out_invdepth) + tail
-                self.api.call("forward_status", C.byref(s), status.data_ptr(), stream)
-                cur.synchronize()
-                if int(status[2]) != 0:  # some tile needed entries that were cut: forget the limits, do the view again
-                    self.depth_limit_stats["failed"] += 1
-                    cache["limit_ok"] = False
-                    self.limits_failed(cache)
-                    del binning
-                    continue
-                self.limits_held(cache)
-            remember(s)
-            return (num_rendered, out_color, radii, geom, binning, img, out_invdepth) + tail
+        self._pinned = f.status = status  # (last used: read by bench.py for the instance count of the last view)
+        num_rendered, binning = self._forward_lists(f, limit, request == "defer")
+        return (num_rendered, out_color, radii, geom, binning, img, out_invdepth) + tail
 
     REGION_MAX_ENTRIES = 16384  # csrc/gs_common.h RG_MAX_ENTRIES
     REGION_AUTO_MAX = 13000     # binning = "auto": instances of capacity per region above which un-limited forwards take the LSD path
 
-    def _forward_region(self, P, W, H, cache, limit, defer, static, status, cur, geom, img, view, g, radii, stream,
-                        new_binning, scratch_of, render, remember):
-        """The forward with region binning (GsView.tile_cull = 2, csrc/gs_regionbin.hip).  The region buckets live in the
-        binning buffer, so it is allocated BEFORE the geometry phase, from the capacity the previous views needed; the
-        instance count is known once the lists are built (gs_forward_bin copies the status words out), which is what
-        the host waits for - the blend is already running then.  Too small a capacity (or a bucket that overflowed)
-        sets the overflow flag: nothing valid was produced and the view is rendered again with what the status asks for.
-        -> (num_rendered, binning buffer), or None when a region holds more Gaussians than one workgroup can sort."""
-        regions = ((((W + 15) // 16) + 3) // 4) * ((((H + 15) // 16) + 3) // 4)
+    def _forward_lists(self, f, limit, defer):
+        """Instance lists and blend of a forward on the GPU: with the camera's depth `limit` (when there is one), then - if
+        the blend found a tile that needed entries the limits cut - again without.  -> (num_rendered, binning buffer)
 
-        def needed(st):
-            return max(int(st[0]), int(st[3]) * regions)
-
-        def geometry(s):
-            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(s), radii.data_ptr(), None, stream)
-
-        if static:
-            cap = max(int(self.static_capacity), regions)
-            binning = new_binning(cap)
-            s = scratch_of(binning, cap, limit)
-            geometry(s)
-            self.api.call("forward_bin", C.byref(view), C.byref(g), C.byref(s), None, stream)
-            if self.STATUS_IN_RENDER:
-                s.status_host = status.data_ptr()   # the forward's last kernel delivers the status block (+ tag) itself
-            render(s)   # (tile_order stays in line here: inside a captured graph the extra cross-stream edge costs more than the
-            #              kernel it takes off the chain - C3 replay 0.96 -> 1.00 ms; the eager step below gains 6-10 us)
-            if limit is not None:
-                self.depth_limit_stats["used"] += 1
-            if not self.STATUS_IN_RENDER:
-                self.api.call("forward_status", C.byref(s), status.data_ptr(), stream)
-            remember(s)
-            return cap, binning
-
-        limits = (limit, None) if limit is not None else (None,)
-        for limit in limits:
-            limited = limit is not None
-            hint = self._capacity_hint_limited if (limited and self._capacity_hint_limited > 0) else self._capacity_hint
-            cap = hint if hint > 0 else max(8 * P, 1 << 20)
-            for attempt in range(6):
-                cap = max(cap, regions)
-                binning = new_binning(cap)
-                s = scratch_of(binning, cap, limit)
-                geometry(s)
-                if limited and defer:
-                    # the caller collects the verdict (capacity AND limits) later: no host wait at all in this forward
-                    self.api.call("forward_bin", C.byref(view), C.byref(g), C.byref(s), None, stream)
-                    ring = self._status_ring.setdefault(cur.device.index if hasattr(cur, "device") else 0, [[], 0])
-                    if len(ring[0]) < 8:
-                        ring[0].append(torch.zeros((16,), dtype=torch.int32).pin_memory())
-                    block = ring[0][ring[1] % len(ring[0])]
-                    ring[1] += 1
-                    if self.STATUS_IN_RENDER:   # the forward's last kernel writes the status words into the pinned block
-                        s.status_host = block.data_ptr()
-                    split = self._split_tile_order(s)
-                    render(s)
-                    self.depth_limit_stats["used"] += 1
-                    if not self.STATUS_IN_RENDER:
-                        self.api.call("forward_status", C.byref(s), block.data_ptr(), stream)
-                    if split:
-                        done = self._tile_order_on_side(view, s, cur)   # (the status block arrives with that kernel)
+        The verdict on the limits is known once the blend has finished.  The host waits for it here unless it goes to a
+        status block for later: the capture-safe mode's (static_capacity: fixed capacity, no host wait, no host read, no
+        re-run; num_rendered is the capacity and the caller reads last_status() once the stream has drained) or a deferred
+        one (`defer`: a block of the status ring, collected with take_deferred)."""
+        for lim in ((limit, None) if limit is not None else (None,)):
+            deferred = defer and lim is not None and not f.static
+            block = self._status_block(f.device) if deferred else (f.status if f.static else None)
+            if f.view.tile_cull == 2:
+                num_rendered, binning, s = self._lists_region(f, lim, block)
+                if binning is None:
+                    # a region holds more Gaussians than one workgroup sorts: this size goes through the LSD path from now on
+                    f.view.tile_cull = 1
+                    return self._forward_lists(f, limit, defer)
+            else:
+                num_rendered, binning, s = self._lists_lsd(f, lim)
+            if lim is not None:
+                self.depth_limit_stats["used"] += 1   # (capture-safe mode: at capture time only, replays do not pass here)
+            if block is not None:
+                if not s.status_host:   # (unless the forward's last kernel delivers the status block itself)
+                    self.api.call("forward_status", C.byref(s), block.data_ptr(), f.stream)
+                if deferred:
+                    if s.defer_tile_order:
+                        done = self._tile_order_on_side(f.view, s, f.cur)   # (the status block arrives with that kernel)
                     else:
                         done = torch.cuda.Event()
-                        done.record(cur)
-                    self.deferred = dict(status=block, event=done, cache=cache, regions=regions, limited=True, size=(P, W, H, True))
-                    remember(s)
-                    return cap, binning
-                self.api.call("forward_bin", C.byref(view), C.byref(g), C.byref(s), status.data_ptr(), stream)
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                render(s)
-                ev.synchronize()  # the lists are built (the blend is running): did they fit?
-                st = tuple(int(x) for x in status[:4])
-                if st[1] == 0:
-                    break
-                if st[3] > self.REGION_MAX_ENTRIES:
-                    self._region_off.add((P, W, H, limited))
-                    return None
-                cap = int(needed(st) * 1.25) + 4096
-                del binning
-            else:
-                raise RuntimeError("region binning: the capacity did not settle (status %r)" % (st,))
-            self._update_hint(needed(st), limited=limited)
-            num_rendered = st[0]
-            if limited:
-                # depth-limited lists: the blend checks that every bounded tile saturated inside the part of its list
-                # that is certainly complete; the host has to know before it hands the image out
-                self.depth_limit_stats["used"] += 1
-                self.api.call("forward_status", C.byref(s), status.data_ptr(), stream)
-                cur.synchronize()
-                if int(status[2]) != 0:
+                        done.record(f.cur)
+                    # (regions = 0: LSD lists, whose capacity this forward has checked already)
+                    self.deferred = dict(status=block, event=done, cache=f.cache, size=(f.P, f.W, f.H, True),
+                                         regions=_regions(f.W, f.H) if f.view.tile_cull == 2 else 0)
+            elif lim is not None:
+                # depth-limited lists: the blend has checked that every bounded tile saturated inside the part of its
+                # list that is certainly complete; the host has to know before it hands the image out (this wait ends
+                # when the blend does, the un-limited path's when the lists are built)
+                self.api.call("forward_status", C.byref(s), f.status.data_ptr(), f.stream)
+                f.cur.synchronize()
+                if int(f.status[2]) != 0:  # some tile needed entries that were cut: forget the limits, do the view again
                     self.depth_limit_stats["failed"] += 1
-                    cache["limit_ok"] = False
-                    self.limits_failed(cache)
+                    f.cache["limit_ok"] = False
+                    self.limits_failed(f.cache)
                     del binning
                     continue
-                self.limits_held(cache)
-            remember(s)
+                self.limits_held(f.cache)
+            if f.use_order:
+                f.cache["order_ok"] = True
+            if f.use_limit:
+                f.cache["limit_ok"] = True
             return num_rendered, binning
 
-    def _split_tile_order(self, scratch):
-        """Arm GsScratch.defer_tile_order for the render about to be issued?  Only inside a train step (a fused step is armed:
-        its backward is what waits for the side launch) and only with the status delivered by that kernel."""
-        if not (self.SPLIT_TILE_ORDER and self.fused_step is not None and self.STATUS_IN_RENDER):
-            return False
-        scratch.defer_tile_order = 1
-        return True
+    def _lists_lsd(self, f, limit):
+        """Lists by depth sort + emission + partition by tile (GsView.tile_cull = 0 / 1, csrc/gs_binning.hip): the geometry
+        phase counts the instances, the binning buffer is sized by that count.  -> (num_rendered, binning buffer, scratch)"""
+        self.api.call("forward_geometry", C.byref(f.view), C.byref(f.g), C.byref(self._scratch_of(f, f.empty, 0, limit)),
+                      f.radii.data_ptr(), f.status.data_ptr(), f.stream)
+        if f.static:
+            cap = int(self.static_capacity)
+            binning = self._new_binning(f, cap)
+            s = self._scratch_of(f, binning, cap, limit)
+            self._render(f, s)
+            return cap, binning, s
+        cap = self._capacity_hint if self.optimistic else 0
+        if cap > 0 and limit is not None and self._capacity_hint_limited > 0:
+            cap = self._capacity_hint_limited
+        binning = None
+        if cap > 0:
+            # Optimistic path: the reference blocks the host on a D2H copy of num_rendered before it can
+            # size the binning buffer (rasterizer_impl.cu:284-288) and the GPU idles meanwhile.  Here the
+            # binning/blend phase is enqueued at once with a capacity predicted from the previous calls
+            # (the kernels read num_rendered on the device); the host then waits only for the geometry
+            # phase - the GPU is already sorting and blending - and re-runs the phase in the rare case
+            # the prediction was too small.
+            ev = torch.cuda.Event()
+            ev.record(f.cur)
+            binning = self._new_binning(f, cap)
+            s = self._scratch_of(f, binning, cap, limit)
+            self._render(f, s)
+            ev.synchronize()
+        else:
+            f.cur.synchronize()  # the reference's blocking D2H (rasterizer_impl.cu:284)
+        num_rendered = int(f.status[0])
+        self._update_hint(num_rendered, limited=limit is not None)
+        if binning is None or num_rendered > cap:
+            binning = self._new_binning(f, num_rendered)
+            s = self._scratch_of(f, binning, num_rendered, limit)
+            self._render(f, s)
+        return num_rendered, binning, s
+
+    def _lists_region(self, f, limit, block):
+        """Lists by region binning (GsView.tile_cull = 2, csrc/gs_regionbin.hip).  The region buckets live in the binning
+        buffer, so it is allocated BEFORE the geometry phase, from the capacity the previous views needed; the instance count
+        is known once the lists are built (gs_forward_bin copies the status words out), which is what the host waits for -
+        the blend is already running then.  Too small a capacity (or a bucket that overflowed) sets the overflow flag:
+        nothing valid was produced and the view is rendered again with what the status asks for.  With a status `block` the
+        host waits for nothing: whoever reads the block checks capacity and limits alike.
+        -> (num_rendered, binning buffer, scratch); the buffer is None when a region holds more Gaussians than one workgroup
+        can sort."""
+        regions = _regions(f.W, f.H)
+        limited = limit is not None
+        if f.static:
+            cap = int(self.static_capacity)
+        else:
+            hint = self._capacity_hint_limited if (limited and self._capacity_hint_limited > 0) else self._capacity_hint
+            cap = hint if hint > 0 else max(8 * f.P, 1 << 20)
+        for attempt in range(6):
+            cap = max(cap, regions)
+            binning = self._new_binning(f, cap)
+            s = self._scratch_of(f, binning, cap, limit)
+            self.api.call("forward_geometry", C.byref(f.view), C.byref(f.g), C.byref(s), f.radii.data_ptr(), None, f.stream)
+            if block is not None:
+                self.api.call("forward_bin", C.byref(f.view), C.byref(f.g), C.byref(s), None, f.stream)
+                if self.STATUS_IN_RENDER:   # the forward's last kernel writes the status words into the pinned block
+                    s.status_host = block.data_ptr()
+                    # Train step (a fused step is armed): that kernel (tile_order: the backward's launch order, the camera's
+                    # next hints and depth bounds, the status block) is issued on the SIDE stream - nothing before the
+                    # backward blend needs it, so it runs beside the criterion's first kernel instead of in front of it; the
+                    # backward waits for it.  Not in the capture-safe mode: inside a captured graph the extra cross-stream
+                    # edge costs more than the kernel it takes off the chain (C3 replay 0.96 -> 1.00 ms; the eager step
+                    # gains 6-10 us).
+                    if self.fused_step is not None and not f.static:
+                        s.defer_tile_order = 1
+                self._render(f, s)
+                return cap, binning, s
+            self.api.call("forward_bin", C.byref(f.view), C.byref(f.g), C.byref(s), f.status.data_ptr(), f.stream)
+            ev = torch.cuda.Event()
+            ev.record(f.cur)
+            self._render(f, s)
+            ev.synchronize()  # the lists are built (the blend is running): did they fit?
+            st = tuple(int(x) for x in f.status[:4])
+            if st[1] == 0:
+                break
+            if st[3] > self.REGION_MAX_ENTRIES:
+                self._region_off.add((f.P, f.W, f.H, limited))
+                return 0, None, None
+            cap = int(max(st[0], st[3] * regions) * 1.25) + 4096
+            del binning
+        else:
+            raise RuntimeError("region binning: the capacity did not settle (status %r)" % (st,))
+        self._update_hint(max(st[0], st[3] * regions), limited=limited)
+        return st[0], binning, s
+
+    def _status_block(self, device):
+        """A pinned status block for a verdict collected later, from a small ring per device: a block is re-used only after
+        eight further deferred forwards."""
+        ring = self._status_ring.setdefault(device.index, [[], 0])
+        if len(ring[0]) < 8:
+            ring[0].append(torch.zeros((16,), dtype=torch.int32).pin_memory())
+        block = ring[0][ring[1] % len(ring[0])]
+        ring[1] += 1
+        return block
+
+    def _new_binning(self, f, cap):
+        _, _, bb, _ = self.scratch_bytes(f.P, f.W, f.H, cap)
+        binning = torch.empty((bb,), dtype=torch.uint8, device=f.device)
+        if self.scratch_fill is not None:
+            self.scratch_fill("binning", binning)
+        self._remember_capacity(binning, cap)
+        return binning
+
+    def _scratch_of(self, f, binning, capacity, limit):
+        s = self._scratch(f.geom, f.img, binning, capacity)
+        if limit is not None:
+            s.tile_depth_limit = limit.data_ptr()
+        if f.static and self.static_step_tag is not None:
+            s.step_tag = self.static_step_tag.data_ptr()
+        return s
+
+    def _render(self, f, scratch):
+        c = f.cache
+        if f.use_order:
+            if c["order_ok"]:
+                scratch.tile_order_hint = c["order"].data_ptr()
+            # what this view measures becomes the hint of this camera's next visit: written by the forward's last launch
+            # straight into the camera's buffers (they are read - as this view's hints - before they are written)
+            scratch.tile_order_out = c["order"].data_ptr()
+        if f.use_limit:
+            scratch.tile_depth_limit_out = c["limit"].data_ptr()
+            scratch.tile_depth_limit_slack = c["slack"].data_ptr()
+        if f.fsgs:
+            self.api.call("forward_render_fsgs", C.byref(f.view), C.byref(f.g), C.byref(scratch), f.out_color.data_ptr(),
+                          f.out_invdepth.data_ptr(), f.out_extra.data_ptr(), f.stream)
+        elif f.extra is None:
+            self.api.call("forward_render", C.byref(f.view), C.byref(f.g), C.byref(scratch), f.out_color.data_ptr(),
+                          f.out_invdepth.data_ptr(), f.stream)
+        else:
+            self.api.call("forward_render_x", C.byref(f.view), C.byref(f.g), C.byref(scratch), f.out_color.data_ptr(),
+                          f.out_invdepth.data_ptr(), f.out_extra.data_ptr(), f.stream)
 
     def _tile_order_on_side(self, view, scratch, main):
         """gs_forward_tile_order on the side stream, ordered behind the render just issued on `main`; the event it returns (also
@@ -858,17 +839,6 @@ class RasterBackend:
         if done is not None:
             torch.cuda.current_stream(device).wait_event(done)
 
-    def _render(self, scratch, fsgs, extra, view, g, out_color, out_invdepth, out_extra, stream):
-        if fsgs:
-            self.api.call("forward_render_fsgs", C.byref(view), C.byref(g), C.byref(scratch), out_color.data_ptr(),
-                          out_invdepth.data_ptr(), out_extra.data_ptr(), stream)
-        elif extra is None:
-            self.api.call("forward_render", C.byref(view), C.byref(g), C.byref(scratch), out_color.data_ptr(),
-                          out_invdepth.data_ptr(), stream)
-        else:
-            self.api.call("forward_render_x", C.byref(view), C.byref(g), C.byref(scratch), out_color.data_ptr(),
-                          out_invdepth.data_ptr(), out_extra.data_ptr(), stream)
-
     # ------------------------------------------------------------------ backward
     def rasterize_gaussians_backward(self, bg, means3D, radii, colors_precomp, opacities, scales, rotations,
                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy,
@@ -884,7 +854,6 @@ class RasterBackend:
         device = means3D.device
         P = int(means3D.shape[0])
         H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])
-        self._region_key = None
         if device.type == "cuda":
             self._join_tile_order(device)   # (the blend backward reads the launch order that kernel writes)
         M = int(sh.shape[1]) if (sh is not None and sh.numel() != 0) else 0
@@ -906,15 +875,9 @@ class RasterBackend:
         if step is not None and P != 0:
             if fsgs:
                 raise RuntimeError("the fused train-step backward does not serve the FSGS rasterizer generation")
-            built = getattr(self, "_built", None)
-            if self.REUSE_BUILT and built is not None and built["geom"] == geomBuffer.data_ptr() and built["raw"] == raw:
-                view, g, keep = built["view"], built["g"], built["keep"]   # (this view's forward built them: same pointers)
-            else:
-                keep = []
-                view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
-                                  degree, False, antialiasing, debug)
-                g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra,
-                                raw=raw, extra_gain=extra_gain, sh_rest=sh_rest)
+            view, g, keep = self._structs(geomBuffer, raw, bg, means3D, sh, colors_precomp, opacities, scales, rotations,
+                                          cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
+                                          degree, antialiasing, debug, extra, extra_gain, sh_rest)
             if extra is not None:
                 dL_dout_extra = torch.zeros((1, H, W), **f32) if dL_dout_extra is None else _prep(dL_dout_extra, device)
             dL_dout_color = _prep(dL_dout_color, device)

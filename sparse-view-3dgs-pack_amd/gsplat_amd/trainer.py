@@ -1245,7 +1245,7 @@ class Trainer:
             loss, parts = self.criterion.fused_call(pkg["render"], self.gts[ci], mask=mask)
             loss, parts = self._depth_term(pkg, ci, loss, parts)
             # two-phase step: the Adam stream of the Gaussians without instances starts on its side stream from inside the
-            # criterion's backward (RasterBackend.UNINST_AT) - it needs nothing of the loss - and runs beside the blend
+            # criterion's backward (_arm_side_launch) - it needs nothing of the loss - and runs beside the blend
             self._arm_side_launch(side_launch)
             # (seeded with the criterion's cached constant 1: no fill kernel for the implicit seed, no multiply by it)
             torch.autograd.backward(loss, self.criterion.ops.unit_grad(loss.device))
@@ -1256,15 +1256,9 @@ class Trainer:
         return loss, parts
 
     def _arm_side_launch(self, side_launch):
-        ops = self.criterion.ops
-        ops.before_last_backward_kernel = None
-        if side_launch is None:
-            return
-        backend = self._backend()
-        if backend.UNINST_AT == "ssim_backward":      # ... between the criterion's two backward kernels
-            ops.before_last_backward_kernel = side_launch
-        else:
-            side_launch()
+        # the criterion's backward issues it before its last kernel (ssim_bwd): C3 0.983 ms/step, against 1.024 issued before
+        # the criterion's backward and 1.01-1.15 at the start of the rasterizer's backward (no head start on the blend)
+        self.criterion.ops.before_last_backward_kernel = side_launch
 
     def _unfused_tail(self, pkg, radii, optimizer_step, skip):
         m = self.model
