@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - train-step views/s (fwd+bwd) of the MI355X rasterizer + LGDWT loss path.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c2|c1|c5|tiny] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4|c2|c1|c5|tiny] [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
               --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,14 +16,18 @@ optimizer; the metric's "(fwd+bwd)" is BASELINE.json's wording.  Synthetic "trai
 like orbit cameras, inputs resident in HBM before the timed region.  Cameras are sharded over ranks
 and per-GPU work is fixed, so scaling is "weak".
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line, with one extra object that costs no run of its own:
   roofline     for the dominant kernel: algorithmic bytes per launch / mean launch duration measured
-               with HIP events on the launch stream (library profiler, include/gsplat.h gs_profile_*);
-               for the blend kernels (VALU-bound) additionally the VALU-issue fraction, from the instruction
-               counts of the committed SQ-counter profile (labelled with its tag) and this run's duration
-  cpu_baseline the CPU oracle ("port") timed on this box's host cores on the same workload: all cores
+               with HIP events on the launch stream (library profiler, include/gsplat.h gs_profile_*) inside the
+               timed region; for the blend kernels (VALU-bound) additionally the VALU-issue fraction, from the
+               instruction counts of the committed SQ-counter profile (labelled with its tag) and this run's duration
+--full adds the untimed legs after the timed region (the GS_BENCH_* switches in main() and --no-cpu-baseline drop single ones):
+  stages       every stage's HIP-event time in an untimed pass of the same step (and the one-launch form of it)
+  cpu_baseline the CPU oracle ("port") timed on the host cores on the same workload: all cores
                (2 warm-up views, median of 5) and one thread (one view)
   reference_lists  the same step on the reference's bounding-square instance lists (tile_cull = 0)
+  options, drop_in_api, sustained, other_scenes   other options, loops, run lengths and scenes of the same step
 """
 import argparse
 import json
@@ -329,6 +333,9 @@ def main():
     ap.add_argument("--no-stage-timers", action="store_true")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed legs: every stage's timers, the CPU baseline, the "
+                         "reference's lists, the loop options, the drop-in loop, the sustained runs and the other scenes")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -582,6 +589,9 @@ def main():
             api.call("profile_enable", 0)
             prof_timed = read_profile(api)
             api.call("profile_only", -1)
+        # a plain run reports the dominant kernel as the timed region measured it, and nothing that takes a run of its own
+        prof = dict(prof_timed)
+    if not args.no_stage_timers and args.full:
         # every stage, in an untimed eager pass of the same steady-state step right after the timed region
         prof = profile_all_stages(min(args.steps, 10))
         if dom_stage in prof_timed:
@@ -600,7 +610,7 @@ def main():
     # the same step on the reference's bounding-square instance lists (GsView.tile_cull = 0: point_list / ranges /
     # num_rendered bit-identical to the reference's), outside the timed region
     ref_lists = None
-    if world == 1 and os.environ.get("GS_BENCH_REFERENCE_LISTS", "1") != "0":
+    if args.full and world == 1 and os.environ.get("GS_BENCH_REFERENCE_LISTS", "1") != "0":
         from gsplat_amd import hip_backend as _hb
         be = _hb()
         old_cull = be.tile_cull
@@ -633,7 +643,7 @@ def main():
     #    beside the backward blend shrinks to the visible Gaussians without instances;
     #  * the depth-regularisation term (train.py:204-216) with a synthetic monocular prior per camera.
     options = None
-    if world == 1 and args.config not in NIR_CONFIGS and os.environ.get("GS_BENCH_OPTIONS", "1") != "0":
+    if args.full and world == 1 and args.config not in NIR_CONFIGS and os.environ.get("GS_BENCH_OPTIONS", "1") != "0":
         options = {}
         nopt = min(args.steps, 10)
 
@@ -690,7 +700,7 @@ def main():
     # the reference's render() (the model's six raw tensors go to the library, SH rows read where the model keeps them) with
     # the criterion as one node on its un-clamped image (criterion.fused_call).  loss.item() sits where train.py:224 has it.
     drop_in = None
-    if world == 1 and args.config not in NIR_CONFIGS and os.environ.get("GS_BENCH_DROP_IN", "1") != "0":
+    if args.full and world == 1 and args.config not in NIR_CONFIGS and os.environ.get("GS_BENCH_DROP_IN", "1") != "0":
         from gsplat_amd.dropin import DropInLoop
         drop_in = {"what": "LGDWT-GS/train.py:97-288 against the drop-in packages only (gsplat_amd/dropin.py): "
                            "GaussianRasterizer + lgdwt_loss functions + fused_ssim + Adam over six tensors, the reference's "
@@ -738,7 +748,8 @@ def main():
     # (the same scene with slightly different colours: a run that is converging, where training spends its time).
     sustained = None
     n_sus = int(os.environ.get("GS_BENCH_SUSTAINED", "600"))
-    if world == 1 and args.config == "c3" and depth_limit and n_sus > 0 and os.environ.get("GS_BENCH_OTHER_SCENES", "1") != "0":
+    if args.full and world == 1 and args.config == "c3" and depth_limit and n_sus > 0 and \
+            os.environ.get("GS_BENCH_OTHER_SCENES", "1") != "0":
         from gsplat_amd import hip_backend as _hb3
         be3 = _hb3()
         sustained = {}
@@ -790,7 +801,7 @@ def main():
     # not used here: eager, depth limits as in the timed region) on an init-like scene at SH degree 0 and on a scene
     # whose background never saturates - what the depth limits / early termination cannot shortcut
     other = {}
-    if world == 1 and args.config == "c3" and os.environ.get("GS_BENCH_OTHER_SCENES", "1") != "0":
+    if args.full and world == 1 and args.config == "c3" and os.environ.get("GS_BENCH_OTHER_SCENES", "1") != "0":
         from gsplat_amd import hip_backend as _hb2
         for kind in ("init_like", "ball_in_shell"):
             t_b = time.perf_counter()
@@ -911,7 +922,7 @@ def main():
                 e["GBps"] = sb[name] / 1e9 / (ms / cnt / 1e3)
             stages[name] = e
         roofline = None
-        if stages:
+        if any(n in sb for n in stages):   # (a plain run's stages hold the dominant kernel only)
             dom = dom_stage if dom_stage in stages and dom_stage in sb else \
                 max((n for n in stages if n in sb), key=lambda n: stages[n]["ms_per_launch"])
             ach = stages[dom]["GBps"]
@@ -1036,10 +1047,18 @@ def main():
                             "region (each event pair drains the pipeline for ~10 us); the timed region replays the step "
                             "from a hipGraph (%d replays, %d eager fall-backs, %d captures), so no event sits inside it; "
                             "the timed step includes the optimizer" % (graphed.replays, graphed.eager_steps, graphed.captures))
-                           if graphed is not None else
+                           if graphed is not None and args.full else
                            ("HIP events; %s measured inside the timed region (on every 4th step of it), the other stages in a "
                             "separate untimed pass of the same step right after it (each event pair drains the pipeline for ~10 us); "
-                            "the timed step includes the optimizer" % dom_stage),
+                            "the timed step includes the optimizer" % dom_stage)
+                           if args.full else
+                           ("none: the timed region replays the step from a hipGraph (%d replays, %d eager fall-backs, %d "
+                            "captures), so no event sits inside it, and --full adds the untimed eager pass that times every "
+                            "stage; the timed step includes the optimizer" % (graphed.replays, graphed.eager_steps, graphed.captures))
+                           if graphed is not None else
+                           ("HIP events; only %s, measured inside the timed region (on every 4th step of it; each event pair "
+                            "drains the pipeline for ~10 us); --full adds the other stages from a separate untimed pass of the "
+                            "same step; the timed step includes the optimizer" % dom_stage),
             "launch": "hipGraph replay of the captured step" if graphed is not None else "eager",
             "depth_limit": ({"mode": "deferred verdict", "limited_views_in_timed_region": dl1["used"] - dl0["used"],
                              "fallbacks_in_timed_region": dl1["failed"] - dl0["failed"],
@@ -1049,7 +1068,7 @@ def main():
                                      "GS_BENCH_DEPTH_LIMIT=0 = full lists"} if depth_limit else None),
             "launch_trial": graph_choice,
         }
-        if world == 1 and not args.no_cpu_baseline and args.config not in NIR_CONFIGS:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config not in NIR_CONFIGS:
             ci = tr.camera_index(k - 1)
             out["cpu_baseline"] = cpu_baseline(args.config, scene, cams[ci], gts[ci], log)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

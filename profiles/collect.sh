@@ -15,7 +15,7 @@ rm -rf $OUT $SUM
 mkdir -p $OUT $SUM
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --full > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-stage-timers > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-stage-timers > $OUT/bench_write.json 2> $OUT/bench_write.err
 # SQ counters (VALU / LDS / wait shares per kernel), four passes of four counters each
@@ -26,7 +26,7 @@ for c in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY" "SQ_WAIT_INST_ANY 
 done
 # SURVEY 8(d)'s init-like scene as the bench's main scene: kernel trace + the blend kernels' instruction counts
 export GS_BENCH_SCENE=init_like
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_init_like -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_trace_init_like.json 2> $OUT/bench_trace_init_like.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_init_like -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --full > $OUT/bench_trace_init_like.json 2> $OUT/bench_trace_init_like.err
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq_init_like -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-stage-timers > /dev/null 2> $OUT/bench_sq_init_like.err
 unset GS_BENCH_SCENE
 # the two-level binning of tile_cull = 0 (the reference's lists, R = 23 M at C3; csrc/gs_tilebin.hip): forwards only
