@@ -40,20 +40,32 @@ def _regions(W, H):
 
 
 class _Forward:
-    """What the steps of one forward (RasterBackend._rasterize_gaussians) share: its view, Gaussians, buffers, outputs and
+    """What the steps of one forward (RasterBackend.rasterize_gaussians) share: its view, Gaussians, buffers, outputs and
     camera state; on the GPU also its stream and pinned status block."""
-    __slots__ = ("device", "stream", "view", "g", "P", "W", "H", "geom", "img", "empty", "radii", "out_color", "out_invdepth",
+    __slots__ = ("device", "stream", "view", "g", "P", "W", "H", "geom", "img", "radii", "out_color", "out_invdepth",
                  "out_extra", "fsgs", "extra", "cache", "use_order", "use_limit", "static", "cur", "status")
 
     def __init__(self, device, stream, view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs, extra,
                  cache, use_order, use_limit, static):
         self.device, self.stream, self.view, self.g = device, stream, view, g
         self.P, self.W, self.H = P, W, H
-        self.geom, self.img, self.empty, self.radii = geom, img, torch.empty((0,), dtype=torch.uint8, device=device), radii
+        self.geom, self.img, self.radii = geom, img, radii
         self.out_color, self.out_invdepth, self.out_extra = out_color, out_invdepth, out_extra
         self.fsgs, self.extra = fsgs, extra
         self.cache, self.use_order, self.use_limit, self.static = cache, use_order, use_limit, static
         self.cur = self.status = None
+
+
+class _Last:
+    """The last non-empty forward, as its backward finds it - by its geometry buffer, the object itself: the structs it built
+    (and the tensors they point into) and whether it read raw rows.  When it armed the early side launch of a two-phase
+    train step (RasterBackend.launch_uninstanced_early): that `step`, the forward's radii and image buffer, and once the
+    launch is issued its `done` event; a fused backward ends the arming."""
+    __slots__ = ("geom", "P", "view", "g", "keep", "raw", "step", "radii", "img", "done")
+
+    def __init__(self, geom, P, view, g, keep, raw):
+        self.geom, self.P, self.view, self.g, self.keep, self.raw = geom, P, view, g, keep, raw
+        self.step = self.radii = self.img = self.done = None
 
 
 class RasterBackend:
@@ -124,16 +136,13 @@ class RasterBackend:
         self._side_streams = {}
         self._rows_ws = {}        # (device, bytes) -> [persistent gradient-row workspace of the fused step, rows all zero?]
         self.rows_epoch = 0       # bumped whenever a fused backward found (or may have left) that workspace dirty
-        self._built = None        # the GsView / GsGaussians of the last forward (see _structs)
-        self._early = None        # what launch_uninstanced_early needs of the last forward
+        self._last = None         # the last non-empty forward (_Last)
         self.two_phase_launches = 0
         self._uninst_done = None
         # one-shot, set together with fused_step by the train step: the opacities / scales / rotations of the next forward
         # (and of its gs_backward_step) are the model's RAW rows, activated inside the kernels
         # (GsGaussians.raw_activations): no activation kernel, no activated copies
         self.raw_activations = False
-        self._raw_backward = False
-        self._raw_geom = None       # geomBuffer of the last forward on raw rows (whose backward the flag above announces)
         # one-shot, set before a forward / a fused backward on raw rows: the model's _features_rest [P,M-1,3]; `sh` is then
         # _features_dc [P,1,3] (GsGaussians.shs_rest: the kernels read the split rows, no torch.cat)
         self.sh_rest = None
@@ -155,7 +164,7 @@ class RasterBackend:
 
     def _tile_cull(self, device):
         """GsView.tile_cull of this backend's views: 0 = the reference's lists, 1 = culled lists built by the LSD path,
-        2 = by region binning.  (A forward may still take the LSD path for its own lists, see _rasterize_gaussians; the
+        2 = by region binning.  (A forward may still take the LSD path for its own lists, see rasterize_gaussians; the
         backward only asks whether they were culled.)"""
         cull = int(self.tile_cull)
         if cull and self.binning in ("region", "auto") and device.type == "cuda":
@@ -425,11 +434,13 @@ class RasterBackend:
             c["slack"].fill_(self.SLACK[c["slack_level"]])
 
     @staticmethod
-    def _scratch(geom, img, binning, capacity):
+    def _scratch(geom, img=None, binning=None, capacity=0):
         s = GsScratch()
         s.geom, s.geom_bytes = _ptr(geom), geom.numel()
-        s.img, s.img_bytes = _ptr(img), img.numel()
-        s.binning, s.binning_bytes = _ptr(binning), binning.numel()
+        if img is not None:
+            s.img, s.img_bytes = _ptr(img), img.numel()
+        if binning is not None:
+            s.binning, s.binning_bytes = _ptr(binning), binning.numel()
         s.binning_capacity = int(capacity)
         return s
 
@@ -458,52 +469,32 @@ class RasterBackend:
     TWO_PHASE = os.environ.get("GS_TWO_PHASE_STEP", "1") != "0"
     TWO_PHASE_MIN_P = 100_000
 
-    def rasterize_gaussians(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
-                             cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
-                             sh, degree, campos, prefiltered, antialiasing, debug, extra=None, fsgs=False, extra_gain=None):
-        """The forward (see _rasterize_gaussians); with a fused train step armed it also remembers what an early side launch
-        of that step needs (launch_uninstanced_early)."""
-        raw = self.raw_activations
-        out = self._rasterize_gaussians(bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
-                                        cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
-                                        sh, degree, campos, prefiltered, antialiasing, debug, extra=extra, fsgs=fsgs,
-                                        extra_gain=extra_gain)
-        self._early = None
-        step = self.fused_step
-        if step is not None and not fsgs and means3D.device.type == "cuda":
-            P = int(means3D.shape[0])
-            if self.TWO_PHASE and P >= self.TWO_PHASE_MIN_P and not step.grad_out[0] and not step.rows_override:
-                self._early = dict(args=(bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                                         projmatrix, campos, tanfovx, tanfovy, int(image_height), int(image_width),
-                                         scale_modifier, degree, antialiasing, debug, extra, extra_gain),
-                                   raw=raw, radii=out[2], geom=out[3], img=out[5], step=step, done=None)
-        return out
+    def _two_phase(self, step, P):
+        """Does the fused backward of `step` over P Gaussians run in two phases?  (Not its gradients-out form; with
+        rows_override it does, and issues the side launch itself: see _arms_side_launch.)"""
+        return self.TWO_PHASE and P >= self.TWO_PHASE_MIN_P and not step.grad_out[0]
+
+    def _arms_side_launch(self, step, P):
+        """Does a forward whose backward is `step`'s arm the early side launch (launch_uninstanced_early)?  Only without
+        rows_override."""
+        return self._two_phase(step, P) and not step.rows_override
 
     def launch_uninstanced_early(self):
         """Issue the side launch of the two-phase step NOW (everything enqueued so far on the current stream - the forward,
         the criterion's forward - is waited for by the side stream; what the caller enqueues next runs beside it).  No-op
         unless the last forward armed it.  The rasterizer's backward then only waits for it."""
-        e = self._early
-        if e is None or e["done"] is not None:
+        f = self._last
+        if f is None or f.step is None or f.done is not None:
             return False
-        view, g, keep = self._structs(e["geom"], e["raw"], *e["args"])
-        device = e["geom"].device
-        empty = torch.empty((0,), dtype=torch.uint8, device=device)
-        s = self._scratch(e["geom"], e["img"], empty, 0)
-        e["done"] = self._launch_uninstanced(device, view, g, e["radii"], s, e["step"])
-        e["keep"] = keep
+        f.done = self._launch_uninstanced(f.geom.device, f.view, f.g, f.radii, self._scratch(f.geom, f.img), f.step)
         return True
 
-    def _structs(self, geom, raw, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
-                 projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree, antialiasing, debug, extra, extra_gain,
-                 sh_rest=None):
-        """-> (GsView, GsGaussians, tensors they point into) of the view and Gaussians the forward that wrote `geom` served:
-        the structs that forward built (same pointers; the train step's side launch and its backward), else built again."""
-        built = self._built
-        if built is not None and built["geom"] == geom.data_ptr() and built["raw"] == raw:
-            return built["view"], built["g"], built["keep"]
+    def _structs(self, device, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
+                 projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree, antialiasing, debug, extra=None, raw=False,
+                 extra_gain=None, sh_rest=None):
+        """-> (GsView, GsGaussians, tensors they point into) built again for a backward: not prefiltered, the backend's own
+        kind of lists (_tile_cull)."""
         keep = []
-        device = means3D.device
         view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
                           False, antialiasing, debug)
         g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra, raw=raw,
@@ -523,9 +514,9 @@ class RasterBackend:
         self.two_phase_launches += 1
         return done
 
-    def _rasterize_gaussians(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
-                              cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
-                              sh, degree, campos, prefiltered, antialiasing, debug, extra=None, fsgs=False, extra_gain=None):
+    def rasterize_gaussians(self, bg, means3D, colors_precomp, opacities, scales, rotations, scale_modifier,
+                            cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, image_height, image_width,
+                            sh, degree, campos, prefiltered, antialiasing, debug, extra=None, fsgs=False, extra_gain=None):
         """= RasterizeGaussiansCUDA (rasterize_points.cu:35-124).
 
         Returns (num_rendered, color[3,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer,
@@ -553,8 +544,8 @@ class RasterBackend:
         tail = () if out_extra is None else (out_extra,)
         # (the one-shot requests of this forward are taken here, whatever follows: an empty model must not leave them armed)
         raw, self.raw_activations = self.raw_activations, False
-        self._raw_backward = raw and P != 0
         sh_rest, self.sh_rest = self.sh_rest, None
+        self._last = None
         if P == 0:  # rasterize_points.cu:88
             self.camera_key, self.camera_key_limits, self.depth_limit_request = None, False, None
             e = torch.empty((0,), **u8)
@@ -592,21 +583,22 @@ class RasterBackend:
 
         gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
         geom = torch.empty((gb,), **u8)
-        self._raw_geom = geom.data_ptr() if raw else None
         img = torch.empty((ib,), **u8)
         if self.scratch_fill is not None:
             self.scratch_fill("geom", geom)
             self.scratch_fill("img", img)
         # (the train step's side launch and its backward describe the same view and the same Gaussians: they take these
-        #  structs - and the tensors `keep` holds alive - instead of building them again; keyed by this forward's geometry buffer)
-        self._built = dict(geom=geom.data_ptr(), view=view, g=g, keep=keep, raw=raw)
-        self._last_geom = (geom, P)   # (export_row_mask: the data-parallel step's early mask exchange)
+        #  structs - and the tensors `keep` holds alive - instead of building them again)
+        last = self._last = _Last(geom, P, view, g, keep, raw)
+        step = self.fused_step
+        if step is not None and not fsgs and device.type == "cuda" and self._arms_side_launch(step, P):
+            last.step, last.radii, last.img = step, radii, img
         f = _Forward(device, self._stream(device), view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs,
                      extra, cache, cache is not None and self.order_hint_on, use_limit, static)
 
         if device.type != "cuda":
             nr = (C.c_int32 * 1)()
-            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(self._scratch_of(f, f.empty, 0, None)),
+            self.api.call("forward_geometry", C.byref(view), C.byref(g), C.byref(self._scratch_of(f, None, 0, None)),
                           radii.data_ptr(), C.cast(nr, C.c_void_p), f.stream)
             num_rendered = int(nr[0])
             binning = self._new_binning(f, num_rendered)
@@ -683,7 +675,7 @@ class RasterBackend:
     def _lists_lsd(self, f, limit):
         """Lists by depth sort + emission + partition by tile (GsView.tile_cull = 0 / 1, csrc/gs_binning.hip): the geometry
         phase counts the instances, the binning buffer is sized by that count.  -> (num_rendered, binning buffer, scratch)"""
-        self.api.call("forward_geometry", C.byref(f.view), C.byref(f.g), C.byref(self._scratch_of(f, f.empty, 0, limit)),
+        self.api.call("forward_geometry", C.byref(f.view), C.byref(f.g), C.byref(self._scratch_of(f, None, 0, limit)),
                       f.radii.data_ptr(), f.status.data_ptr(), f.stream)
         if f.static:
             cap = int(self.static_capacity)
@@ -844,96 +836,129 @@ class RasterBackend:
                                      scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy,
                                      dL_dout_color, dL_dout_invdepth, sh, degree, campos, geomBuffer, R,
                                      binningBuffer, imgBuffer, antialiasing, debug, extra=None, dL_dout_extra=None,
-                                     fsgs=False, extra_gain=None):
+                                     fsgs=False, extra_gain=None, raw=False):
         """= RasterizeGaussiansBackwardCUDA (rasterize_points.cu:126-223).
 
         Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
         dL_drotations) (+ dL_dextra [P] when the forward blended a 4th channel).
-        fsgs=True: dL_dout_invdepth is the depth image gradient and dL_dout_extra the alpha image gradient."""
+        fsgs=True: dL_dout_invdepth is the depth image gradient and dL_dout_extra the alpha image gradient.
+        raw=True: the forward read raw rows (GsGaussians.raw_activations) - said by a caller whose forward may not be the last
+        one; the last forward's own record says it for its backward."""
         self._check_device(means3D)
         device = means3D.device
         P = int(means3D.shape[0])
         H, W = int(dL_dout_color.shape[1]), int(dL_dout_color.shape[2])
         if device.type == "cuda":
             self._join_tile_order(device)   # (the blend backward reads the launch order that kernel writes)
-        M = int(sh.shape[1]) if (sh is not None and sh.numel() != 0) else 0
-        f32 = dict(dtype=torch.float32, device=device)
-        # every row is written by gs_backward (culled rows become 0): empty, not zeros
-        alloc = torch.empty if P != 0 else torch.zeros
         arena, self.grad_arena = self.grad_arena, None
         step, self.fused_step = self.fused_step, None
-        raw, self._raw_backward = self._raw_backward, False
-        if raw and step is None and self._raw_geom is not None and self._raw_geom != geomBuffer.data_ptr():
-            # this backward belongs to an EARLIER forward on activated values; the raw forward in between (an evaluation render
-            # under no_grad, say) has no backward of its own
-            raw = False
         sh_rest, self.sh_rest = self.sh_rest, None
+        f = self._last if self._last is not None and self._last.geom is geomBuffer else None
+        if f is not None:
+            raw = f.raw
         if sh_rest is not None and (step is None or not raw or not step.grad_out_rest):
             raise RuntimeError("split SH rows: the backward is gs_backward_step's gradients-out form with grad_out_rest")
         if raw and (step is None or P == 0):
             raise RuntimeError("a forward on raw activations must be followed by the fused train-step backward")
-        if step is not None and P != 0:
-            if fsgs:
-                raise RuntimeError("the fused train-step backward does not serve the FSGS rasterizer generation")
-            view, g, keep = self._structs(geomBuffer, raw, bg, means3D, sh, colors_precomp, opacities, scales, rotations,
-                                          cov3D_precomp, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
-                                          degree, antialiasing, debug, extra, extra_gain, sh_rest)
-            if extra is not None:
-                dL_dout_extra = torch.zeros((1, H, W), **f32) if dL_dout_extra is None else _prep(dL_dout_extra, device)
-            dL_dout_color = _prep(dL_dout_color, device)
-            dL_dout_invdepth = _prep(dL_dout_invdepth, device)
-            _, _, _, wsb = self.scratch_bytes(P, W, H, R)
-            # (the backward clears only the rows of Gaussians that emitted instances; a probe that reads the rows gets zeros
-            # for the others too)
-            two_phase = self.TWO_PHASE and P >= self.TWO_PHASE_MIN_P and not step.grad_out[0]
-            if self.keep_workspace or step.rows_override:
-                ws = (torch.zeros if self.keep_workspace else torch.empty)((wsb,), dtype=torch.uint8, device=device)
-                if self.keep_workspace:
-                    self.last_workspace = ws
-                step.rows_clean = 0
+        fused = step is not None and P != 0
+        if fused and fsgs:
+            raise RuntimeError("the fused train-step backward does not serve the FSGS rasterizer generation")
+        dL_dout_color, dL_dout_invdepth = _prep(dL_dout_color, device), _prep(dL_dout_invdepth, device)
+        # dL_dout_extra from here on: the 4th channel's image gradient (zeros when not given); with fsgs the alpha image's;
+        # else None
+        if extra is not None:
+            dL_dout_extra = _prep(dL_dout_extra, device)
+            if dL_dout_extra is None:
+                dL_dout_extra = torch.zeros((1, H, W), dtype=torch.float32, device=device)
+        elif not fsgs:
+            dL_dout_extra = None
+        if fused and f is not None:
+            view, g = f.view, f.g   # (the forward's own structs: its prefiltered flag and its kind of lists)
+        else:   # (`keep` holds what they point into until the backward has been issued)
+            view, g, keep = self._structs(device, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                          viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
+                                          antialiasing, debug, extra, raw=raw, extra_gain=extra_gain if raw else None,
+                                          sh_rest=sh_rest)
+        args = (view, g, radii.contiguous(), geomBuffer, binningBuffer, imgBuffer, P, W, H, R, dL_dout_color, dL_dout_invdepth,
+                dL_dout_extra)
+        if fused:
+            return self._backward_step(step, f, *args)
+        return self._backward_grads(arena, fsgs, *args)
+
+    def _backward_step(self, step, f, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color, dL_dout_invdepth,
+                       dL_dout_extra):
+        """gs_backward_step[_x] for the train step armed as `step` (backward, activation backward, view statistics and Adam
+        in one per-Gaussian kernel - or its gradients-out form); `f`: the forward's record when it is the last one.
+        Returns no gradients at all."""
+        device = radii.device
+        _, _, _, wsb = self.scratch_bytes(P, W, H, R)
+        ws = self._rows_workspace(step, device, wsb)
+        s = self._scratch(geom, img, binning, self._capacity_for(binning, P, W, H, R))
+        done, last = None, self._last
+        if last is not None:   # (a fused backward ends the last forward's arming, whichever forward it belongs to)
+            if last is f and last.step is step:
+                done = last.done          # (issued by launch_uninstanced_early, under the criterion's backward)
+            last.step = last.radii = last.img = last.done = None
+        if self._two_phase(step, P):
+            if done is None:
+                done = self._launch_uninstanced(device, view, g, radii, s, step)
+            self._uninst_done = done          # (kept alive until the next step replaces it)
+            step.phase = 2                    # gs_backward_step: the Gaussians with instances only ...
+            step.phase1_done = done.cuda_event  # ... its per-Gaussian kernel behind the side launch
+        try:
+            if dL_dout_extra is not None:
+                self.api.call("backward_step_x", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
+                              dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), dL_dout_extra.data_ptr(), C.byref(step),
+                              _ptr(ws), ws.numel(), self._stream(device))
             else:
-                # one persistent workspace per size: the chain kernel zeroes every row it consumes (GsStepState.rows_clean),
-                # so the rows are clean again after every step and no clear launch runs.  rows_clean = 1 - one clear launch,
-                # then clean again - whenever the host is not SURE of that state (first use, a call that raised)
-                key = (device.index, wsb)
-                ent = self._rows_ws.get(key)
-                if ent is None:
-                    if len(self._rows_ws) >= 4:   # (sizes of a model that has since been densified: nothing replays them,
-                        self._rows_ws.clear()    #  a captured graph is keyed by the number of Gaussians)
-                    ent = self._rows_ws[key] = [torch.zeros((wsb,), dtype=torch.uint8, device=device), True]
-                ws = ent[0]
-                # (a launch captured into a hipGraph is replayed with this flag frozen: `rows_epoch` counts the calls that may
-                #  have left rows dirty, GraphedStep keys its graphs by it and captures again - after an eager step that cleaned)
-                step.rows_clean = 2 if ent[1] else 1
-                if not ent[1]:
-                    self.rows_epoch += 1
-                ent[1] = False      # (until the call below has returned: a failed launch leaves them in an unknown state)
-            s = self._scratch(geomBuffer, imgBuffer, binningBuffer, self._capacity_for(binningBuffer, P, W, H, R))
-            early, self._early = self._early, None
-            if two_phase:
-                if early is not None and early["done"] is not None and early["geom"].data_ptr() == geomBuffer.data_ptr() \
-                        and early["step"] is step:
-                    done = early["done"]          # (issued by launch_uninstanced_early, under the criterion's backward)
-                else:
-                    done = self._launch_uninstanced(device, view, g, radii, s, step)
-                self._uninst_done = done          # (kept alive until the next step replaces it)
-                step.phase = 2                    # gs_backward_step: the Gaussians with instances only ...
-                step.phase1_done = done.cuda_event  # ... its per-Gaussian kernel behind the side launch
-            try:
-                if extra is not None:
-                    self.api.call("backward_step_x", C.byref(view), C.byref(g), radii.contiguous().data_ptr(), C.byref(s), int(R),
-                                  dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), dL_dout_extra.data_ptr(), C.byref(step),
-                                  _ptr(ws), ws.numel(), self._stream(device))
-                else:
-                    self.api.call("backward_step", C.byref(view), C.byref(g), radii.contiguous().data_ptr(), C.byref(s), int(R),
-                                  dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), C.byref(step), _ptr(ws), ws.numel(),
-                                  self._stream(device))
-            except Exception:
-                self.rows_epoch += 1   # (the persistent rows may hold sums now: graphs that skip the clear are stale)
-                raise
-            if step.rows_clean:
-                self._rows_ws[(device.index, wsb)][1] = True
-            return (None,) * (8 if extra is None else 9)
+                self.api.call("backward_step", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
+                              dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), C.byref(step), _ptr(ws), ws.numel(),
+                              self._stream(device))
+        except Exception:
+            self.rows_epoch += 1   # (the persistent rows may hold sums now: graphs that skip the clear are stale)
+            raise
+        if step.rows_clean:
+            self._rows_ws[(device.index, wsb)][1] = True
+        return (None,) * (8 if dL_dout_extra is None else 9)
+
+    def _rows_workspace(self, step, device, wsb):
+        """The gradient-row workspace of a fused backward; sets step.rows_clean.  keep_workspace and rows_override: a fresh
+        one (rows_clean = 0).  Otherwise one persistent workspace per size: the chain kernel zeroes every row it consumes
+        (GsStepState.rows_clean), so the rows are clean again after every step and no clear launch runs.  rows_clean = 1 -
+        one clear launch, then clean again - whenever the host is not SURE of that state (first use, a call that raised);
+        the caller marks them clean once the call has returned."""
+        if self.keep_workspace or step.rows_override:
+            step.rows_clean = 0
+            return self._fresh_workspace(device, wsb)
+        key = (device.index, wsb)
+        ent = self._rows_ws.get(key)
+        if ent is None:
+            if len(self._rows_ws) >= 4:   # (sizes of a model that has since been densified: nothing replays them,
+                self._rows_ws.clear()    #  a captured graph is keyed by the number of Gaussians)
+            ent = self._rows_ws[key] = [torch.zeros((wsb,), dtype=torch.uint8, device=device), True]
+        # (a launch captured into a hipGraph is replayed with this flag frozen: `rows_epoch` counts the calls that may
+        #  have left rows dirty, GraphedStep keys its graphs by it and captures again - after an eager step that cleaned)
+        step.rows_clean = 2 if ent[1] else 1
+        if not ent[1]:
+            self.rows_epoch += 1
+        ent[1] = False      # (until the call has returned: a failed launch leaves them in an unknown state)
+        return ent[0]
+
+    def _fresh_workspace(self, device, wsb):
+        # (the backward clears only the rows of Gaussians that emitted instances; a probe that keeps the workspace gets
+        #  zeros for the others too)
+        ws = (torch.zeros if self.keep_workspace else torch.empty)((wsb,), dtype=torch.uint8, device=device)
+        if self.keep_workspace:
+            self.last_workspace = ws
+        return ws
+
+    def _backward_grads(self, arena, fsgs, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color, dL_dout_invdepth,
+                        dL_dout_extra):
+        """gs_backward / _x / _fsgs: the gradients, written into the grad arena's tensors where they fit."""
+        device = radii.device
+        f32 = dict(dtype=torch.float32, device=device)
+        # every row is written by gs_backward (culled rows become 0): empty, not zeros
+        alloc = torch.empty if P != 0 else torch.zeros
 
         def out(name, shape):
             t = None if arena is None else arena.get(name)
@@ -941,48 +966,25 @@ class RasterBackend:
                     and t.dtype == torch.float32:
                 return t
             return alloc(shape, **f32)
-        dL_dmeans3D = out("means3D", (P, 3))
-        dL_dmeans2D = alloc((P, 3), **f32)
         # gradients of inputs that were not given ("absent" colours / covariances) are not produced: the reference
         # returns zero tensors for them (rasterize_points.cu:163-178) which autograd then drops
-        has_colors = colors_precomp is not None and colors_precomp.numel() != 0
-        has_cov = cov3D_precomp is not None and cov3D_precomp.numel() != 0
-        dL_dcolors = alloc((P, NUM_CHANNELS), **f32) if has_colors else None
-        dL_dopacity = alloc((P, 1), **f32)
-        dL_dcov3D = alloc((P, 6), **f32) if has_cov else None
-        dL_dsh = out("sh", (P, M, 3))
-        dL_dscales = alloc((P, 3), **f32)
-        dL_drotations = alloc((P, 4), **f32)
-        ret = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-        dL_dextra = None
-        if extra is not None:
-            dL_dextra = alloc((P,), **f32)
-            ret = ret + (dL_dextra,)
+        dL_dmeans3D = out("means3D", (P, 3))
+        ret = (alloc((P, 3), **f32), alloc((P, NUM_CHANNELS), **f32) if g.colors_precomp else None, alloc((P, 1), **f32),
+               dL_dmeans3D, alloc((P, 6), **f32) if g.cov3D_precomp else None, out("sh", (P, g.M, 3)), alloc((P, 3), **f32),
+               alloc((P, 4), **f32))
+        x = dL_dout_extra is not None and not fsgs   # (a 4th channel)
+        if x:
+            ret = ret + (alloc((P,), **f32),)
         if P == 0:
             return ret
-        keep = []
-        view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier,
-                          degree, False, antialiasing, debug)
-        g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra)
-        stream = self._stream(device)
-        dL_dout_color = _prep(dL_dout_color, device)
-        dL_dout_invdepth = _prep(dL_dout_invdepth, device)
-        radii = radii.contiguous()
         _, _, _, wsb = self.scratch_bytes(P, W, H, R)
-        ws = (torch.zeros if self.keep_workspace else torch.empty)((wsb,), dtype=torch.uint8, device=device)
-        if self.keep_workspace:
-            self.last_workspace = ws
-        cap = self._capacity_for(binningBuffer, P, W, H, R)
-        s = self._scratch(geomBuffer, imgBuffer, binningBuffer, cap)
-        grads = GsGrads()
-        grads.dL_dmeans3D, grads.dL_dmeans2D = dL_dmeans3D.data_ptr(), dL_dmeans2D.data_ptr()
-        grads.dL_dsh = _ptr(dL_dsh)
-        grads.dL_dcolors, grads.dL_dopacity = _ptr(dL_dcolors), dL_dopacity.data_ptr()
-        grads.dL_dscales, grads.dL_drotations = dL_dscales.data_ptr(), dL_drotations.data_ptr()
-        grads.dL_dcov3D = _ptr(dL_dcov3D)
+        ws = self._fresh_workspace(device, wsb)
+        s = self._scratch(geom, img, binning, self._capacity_for(binning, P, W, H, R))
+        grads = self._grads(ret)
         if g.scales is None:
-            dL_dscales.zero_()
-            dL_drotations.zero_()
+            ret[6].zero_()
+            ret[7].zero_()
+        stream = self._stream(device)
         if fsgs:
             zeros = None
             if dL_dout_invdepth is None or _prep(dL_dout_extra, device) is None:
@@ -993,18 +995,25 @@ class RasterBackend:
             self.api.call("backward_fsgs", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
                           dL_dout_color.data_ptr(), gd.data_ptr(), ga.data_ptr(), C.byref(grads), _ptr(ws), ws.numel(),
                           stream)
-        elif extra is None:
+        elif not x:
             self.api.call("backward", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
                           dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), C.byref(grads), _ptr(ws), ws.numel(), stream)
         else:
-            grads.dL_dextra = dL_dextra.data_ptr()
-            dL_dout_extra = _prep(dL_dout_extra, device)
-            if dL_dout_extra is None:
-                dL_dout_extra = torch.zeros((1, H, W), **f32)
             self.api.call("backward_x", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
                           dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), dL_dout_extra.data_ptr(), C.byref(grads),
                           _ptr(ws), ws.numel(), stream)
         return ret
+
+    _GRAD_FIELDS = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dscales",
+                    "dL_drotations", "dL_dextra")
+
+    @classmethod
+    def _grads(cls, ret):
+        """GsGrads over a backward's return tuple (None: a gradient that is not produced)."""
+        grads = GsGrads()
+        for name, t in zip(cls._GRAD_FIELDS, ret):
+            setattr(grads, name, _ptr(t))
+        return grads
 
     def backward_from_rows(self, rows, bg, means3D, radii, colors_precomp, opacities, scales, rotations, scale_modifier,
                            cov3D_precomp, viewmatrix, projmatrix, tanfovx, tanfovy, H, W, sh, degree, campos, geomBuffer,
@@ -1014,46 +1023,29 @@ class RasterBackend:
         self._check_device(means3D)
         device = means3D.device
         P = int(means3D.shape[0])
-        M = int(sh.shape[1]) if (sh is not None and sh.numel() != 0) else 0
         f32 = dict(dtype=torch.float32, device=device)
-        has_colors = colors_precomp is not None and colors_precomp.numel() != 0
-        has_cov = cov3D_precomp is not None and cov3D_precomp.numel() != 0
-        out = dict(means2D=torch.empty((P, 3), **f32), colors=torch.empty((P, 3), **f32) if has_colors else None,
-                   opacity=torch.empty((P, 1), **f32), means3D=torch.empty((P, 3), **f32),
-                   cov3D=torch.empty((P, 6), **f32) if has_cov else None,
-                   sh=torch.empty((P, M, 3), **f32) if M else None, scales=torch.zeros((P, 3), **f32),
-                   rotations=torch.zeros((P, 4), **f32))
-        keep = []
-        view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
-                          False, antialiasing, False)
-        g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp)
-        grads = GsGrads()
-        grads.dL_dmeans3D, grads.dL_dmeans2D = out["means3D"].data_ptr(), out["means2D"].data_ptr()
-        grads.dL_dsh, grads.dL_dcolors, grads.dL_dopacity = _ptr(out["sh"]), _ptr(out["colors"]), out["opacity"].data_ptr()
-        grads.dL_dscales, grads.dL_drotations = out["scales"].data_ptr(), out["rotations"].data_ptr()
-        grads.dL_dcov3D = _ptr(out["cov3D"])
+        view, g, keep = self._structs(device, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp,
+                                      viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, degree,
+                                      antialiasing, False)
+        ret = (torch.empty((P, 3), **f32), torch.empty((P, 3), **f32) if g.colors_precomp else None,
+               torch.empty((P, 1), **f32), torch.empty((P, 3), **f32), torch.empty((P, 6), **f32) if g.cov3D_precomp else None,
+               torch.empty((P, g.M, 3), **f32) if g.M else None, torch.zeros((P, 3), **f32), torch.zeros((P, 4), **f32))
         rows = rows.to(device=device, dtype=torch.float64).contiguous()
         assert rows.shape == (P, 16)
-        s = self._scratch(geomBuffer, torch.empty(0, dtype=torch.uint8, device=device),
-                          torch.empty(0, dtype=torch.uint8, device=device), 0)
         _, _, _, wsb = self.scratch_bytes(P, W, H, 0)
         ws = torch.empty((wsb,), dtype=torch.uint8, device=device)
-        self.api.call("backward_from_rows", C.byref(view), C.byref(g), radii.contiguous().data_ptr(), C.byref(s),
-                      rows.data_ptr(), int(depth_mode), C.byref(grads), ws.data_ptr(), ws.numel(), self._stream(device))
-        return (out["means2D"], out["colors"], out["opacity"], out["means3D"], out["cov3D"], out["sh"], out["scales"],
-                out["rotations"])
+        self.api.call("backward_from_rows", C.byref(view), C.byref(g), radii.contiguous().data_ptr(), C.byref(self._scratch(geomBuffer)),
+                      rows.data_ptr(), int(depth_mode), C.byref(self._grads(ret)), ws.data_ptr(), ws.numel(), self._stream(device))
+        return ret
 
     # ------------------------------------------------------------------ markVisible
     def export_row_mask(self, out):
         """out [P] uint8 <- 1 where the Gaussian emitted instances in the LAST forward (gs_export_row_mask: what the
         data-parallel backward later writes into GsStepState.grad_mask).  False when there is no such forward to ask."""
-        last = getattr(self, "_last_geom", None)
-        if last is None or last[0].device != out.device or last[1] != out.numel() or not hasattr(self.api, "_export_row_mask"):
+        f = self._last
+        if f is None or f.geom.device != out.device or f.P != out.numel() or not hasattr(self.api, "_export_row_mask"):
             return False
-        geom, P = last
-        empty = torch.empty((0,), dtype=torch.uint8, device=geom.device)
-        s = self._scratch(geom, empty, empty, 0)
-        self.api.call("export_row_mask", C.byref(s), P, out.data_ptr(), self._stream(geom.device))
+        self.api.call("export_row_mask", C.byref(self._scratch(f.geom)), f.P, out.data_ptr(), self._stream(f.geom.device))
         return True
 
     def mark_visible(self, means3D, viewmatrix, projmatrix):

@@ -85,13 +85,12 @@ class _RawRender(torch.autograd.Function):
         st.grad_out_rest = grest.data_ptr()
         st.beta1, st.beta2, st.eps = 0.9, 0.999, 1e-15
         st.xyz_gradient_accum, st.denom, st.max_radii2D = stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr()
-        backend._raw_backward = True
         backend.sh_rest = f_rest
         backend.fused_step = st
         e = _empty()
         backend.rasterize_gaussians_backward(rs.bg, xyz, radii, e, opacity, scaling, rotation, rs.scale_modifier, e, rs.viewmatrix,
                                              rs.projmatrix, rs.tanfovx, rs.tanfovy, g_color, g_depth, f_dc, rs.sh_degree,
-                                             rs.campos, geom, ctx.num_rendered, binning, img, rs.antialiasing, rs.debug)
+                                             rs.campos, geom, ctx.num_rendered, binning, img, rs.antialiasing, rs.debug, raw=True)
         vsp[:, 0] = stats[0]
         return gx, gdc, grest, gop, gsc, grot, vsp, None, None, None
 

@@ -95,12 +95,11 @@ def _raw_forward_backward(backend, rs, pc, cot, cot_d, split):
             st.grad_out_rest = gsh[1].data_ptr()
         st.beta1, st.beta2, st.eps = 0.9, 0.999, 1e-15
         st.xyz_gradient_accum, st.denom, st.max_radii2D = (stats[k].data_ptr() for k in range(3))
-        backend._raw_backward = True
         backend.sh_rest = f_rest if split else None
         backend.fused_step = st
         backend.rasterize_gaussians_backward(rs.bg, xyz, radii, e, op, sc, rot, rs.scale_modifier, e, rs.viewmatrix, rs.projmatrix,
                                              rs.tanfovx, rs.tanfovy, cot, cot_d, sh, rs.sh_degree, rs.campos, geom, num_rendered,
-                                             binning, img, rs.antialiasing, rs.debug)
+                                             binning, img, rs.antialiasing, rs.debug, raw=True)
         torch.cuda.synchronize()
     gsh_all = torch.cat(gsh, dim=1)
     return dict(color=color, radii=radii, invdepth=invdepth, gx=gx, gsh=gsh_all, gop=gop, gsc=gsc, grot=grot, stats=stats)
@@ -157,10 +156,11 @@ def test_split_sh_rows_are_refused_where_they_are_not_served(hip):
     assert backend.sh_rest is None
 
 
-def test_an_empty_model_renders_nothing_and_leaves_no_request_armed(hip):
+def test_an_empty_model_renders_nothing_and_leaves_no_forward_or_request_armed(hip):
     """P = 0 (rasterize_points.cu:88: the reference returns zero images and empty buffers): render_raw returns the same, its
-    backward returns empty gradients, and the one-shot requests it made of the backend (raw activations, split SH rows, camera
-    key) are gone - the next, ordinary render is not affected."""
+    backward returns empty gradients, the one-shot requests it made of the backend (raw activations, split SH rows, camera
+    key) are gone, and no forward record is left for a backward or a side launch to find - the next, ordinary render is not
+    affected."""
     from gsplat_amd.render_raw import render as render_raw
     from diff_gaussian_rasterization import _RasterizeGaussians
     dev = torch.device("cuda")
@@ -180,7 +180,8 @@ def test_an_empty_model_renders_nothing_and_leaves_no_request_armed(hip):
     (pkg["render"].sum() + pkg["depth"].sum()).backward()
     assert pc._xyz.grad is None or pc._xyz.grad.numel() == 0
     backend = _RasterizeGaussians._impl.backend
-    assert not backend.raw_activations and backend.sh_rest is None and backend.camera_key is None and not backend._raw_backward
+    assert not backend.raw_activations and backend.sh_rest is None and backend.camera_key is None
+    assert backend._last is None and backend.fused_step is None
     # an ordinary render right behind it: activated values, one SH array - must not be read as raw rows
     full = DropInModel(synthetic.trained_like(2000, seed=2), dev)
     a = render(cam, full, bg)["render"]
@@ -188,9 +189,9 @@ def test_an_empty_model_renders_nothing_and_leaves_no_request_armed(hip):
     assert torch.equal(a, b) and float(a.max()) > 0
 
 
-def test_an_evaluation_render_on_raw_rows_between_a_forward_and_its_backward(hip):
-    """train.py renders test views under no_grad while a training graph may still be alive: a raw-row forward without a backward
-    of its own must not be taken for the forward of the NEXT backward the backend sees."""
+def _evaluation_between_a_forward_and_its_backward(train_render):
+    """The leaves' gradients of `train_render` (a training forward) without and with an evaluation render_raw under no_grad
+    between that forward and its backward: they must be the same bits."""
     from gsplat_amd.render_raw import render as render_raw
     dev = torch.device("cuda")
     sc = synthetic.trained_like(5000, seed=4)
@@ -199,7 +200,7 @@ def test_an_evaluation_render_on_raw_rows_between_a_forward_and_its_backward(hip
     grads = []
     for evaluate in (False, True):
         pc = DropInModel(sc, dev)
-        pkg = render(cams[0], pc, bg)                      # the drop-in render on activated values: a training forward
+        pkg = train_render(cams[0], pc, bg)
         if evaluate:
             with torch.no_grad():
                 img = render_raw(cams[1], pc, _PIPE, bg)["render"]
@@ -207,4 +208,44 @@ def test_an_evaluation_render_on_raw_rows_between_a_forward_and_its_backward(hip
         pkg["render"].square().sum().backward()
         grads.append({k: v.grad.clone() for k, v in leaves(pc).items()})
     for k in grads[0]:
+        assert float(grads[0][k].abs().max()) > 0, k
         assert torch.equal(grads[0][k], grads[1][k]), k
+
+
+def test_an_evaluation_render_on_raw_rows_between_a_forward_and_its_backward(hip):
+    """train.py renders test views under no_grad while a training graph may still be alive: a raw-row forward without a backward
+    of its own must not be taken for the forward of the NEXT backward the backend sees."""
+    _evaluation_between_a_forward_and_its_backward(render)   # the drop-in render on activated values: a training forward
+
+
+def test_an_evaluation_render_on_raw_rows_between_a_raw_forward_and_its_backward(hip):
+    """The same with a render_raw training forward: its backward is on raw rows although its forward is not the last one."""
+    from gsplat_amd.render_raw import render as render_raw
+    _evaluation_between_a_forward_and_its_backward(lambda cam, pc, bg: render_raw(cam, pc, _PIPE, bg))
+
+
+def test_export_row_mask_after_an_empty_forward_finds_no_forward(hip):
+    """export_row_mask reads the last forward; an empty model's forward leaves none to ask."""
+    import math
+    from diff_gaussian_rasterization import _RasterizeGaussians
+    backend = _RasterizeGaussians._impl.backend
+    dev = torch.device("cuda")
+    cam = camera_to(synthetic.orbit_cameras(96, 64)[0], dev)
+    e = torch.Tensor([])
+
+    pc = DropInModel(synthetic.trained_like(700, seed=5), dev)
+
+    def forward(P):
+        with torch.no_grad():
+            backend.rasterize_gaussians(torch.zeros(3, device=dev), pc._xyz[:P], e, torch.sigmoid(pc._opacity[:P]),
+                                        torch.exp(pc._scaling[:P]), torch.nn.functional.normalize(pc._rotation[:P]), 1.0, e,
+                                        cam.world_view_transform, cam.full_proj_transform, math.tan(cam.FoVx * 0.5),
+                                        math.tan(cam.FoVy * 0.5), 64, 96, torch.cat((pc._features_dc, pc._features_rest), 1)[:P],
+                                        3, cam.camera_center, False, False, False)
+
+    mask = torch.zeros((700,), dtype=torch.uint8, device=dev)
+    forward(700)
+    assert backend.export_row_mask(mask)
+    forward(0)
+    assert not backend.export_row_mask(mask[:0])
+    assert not backend.export_row_mask(mask)   # (nor does the forward before the empty one answer)
