@@ -478,6 +478,30 @@ int gs_knn_mean_dist2(const float* xyz /*[P,3]*/, int32_t P, float* out /*[P]*/,
 int gs_knn_mean_dist2_idx(const float* xyz /*[P,3]*/, int32_t P, float* out /*[P]*/,
                           int32_t* nearest /*[P,3]*/, void* tmp, size_t tmp_bytes, void* stream);
 
+/* ---- DNGaussian's input encoders (gridencoder/src/gridencoder.cu, shencoder/src/shencoder.cu), fp32 ----
+ * Grid: inputs [B,D] (D 2..5) in [0,1]; embeddings [n_slots,C] (C 1, 2, 4 or 8); offsets [L+1] device int32 (offsets[L] =
+ * n_slots, L <= 64); S = log2(per_level_scale); H = base resolution; gridtype 0 = hash, 1 = tiled; interp 0 = linear,
+ * 1 = smoothstep.  Level l: scale = exp2(l * S) * H - 1 (the fp32 product l * S, exp2 rounded once to fp32, then fp32
+ * arithmetic), resolution = ceil(scale) + 1.  A point with a coordinate outside [0,1] gets zero output, zero dy_dx and no
+ * embedding gradient.
+ * gs_grid_encode_fwd: outputs [B, L*C]; dy_dx [B,L,D,C] or NULL (what the input gradient needs).
+ * gs_grid_encode_bwd: grad [B, L*C]; grad_embeddings [n_slots,C] (every row written, zero where nothing landed; the same
+ * bits on every run: a stable sort of the (slot, contribution) pairs and a fixed-order segmented sum) or NULL;
+ * grad_inputs [B,D] from dy_dx, or NULL.  tmp: >= gs_grid_encode_tmp_bytes(B, D, L, C, n_slots) bytes of device scratch
+ * when grad_embeddings is given.  B * L * 2^D must stay below 2^32.
+ * SH: inputs [B,3]; degree 1..8; outputs [B, degree^2] = the Cartesian real SH polynomials (r^2 -> 1 forms, evaluated as
+ * written for non-unit inputs); gs_sh_encode_bwd: grad_inputs [B,3] = their gradient against grad [B, degree^2]. */
+size_t gs_grid_encode_tmp_bytes(int64_t B, int32_t D, int32_t L, int32_t C, int64_t n_slots);
+int gs_grid_encode_fwd(const float* inputs, int64_t B, int32_t D, const float* embeddings, int64_t n_slots, int32_t C,
+                       const int32_t* offsets, int32_t L, float S, int32_t H, int32_t gridtype, int32_t align_corners,
+                       int32_t interp, float* outputs, float* dy_dx, void* stream);
+int gs_grid_encode_bwd(const float* grad, const float* inputs, int64_t B, int32_t D, int64_t n_slots, int32_t C,
+                       const int32_t* offsets, int32_t L, float S, int32_t H, int32_t gridtype, int32_t align_corners,
+                       int32_t interp, const float* dy_dx, float* grad_embeddings, float* grad_inputs, void* tmp,
+                       size_t tmp_bytes, void* stream);
+int gs_sh_encode_fwd(const float* inputs, int64_t B, int32_t degree, float* outputs, void* stream);
+int gs_sh_encode_bwd(const float* grad, const float* inputs, int64_t B, int32_t degree, float* grad_inputs, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

@@ -157,6 +157,12 @@ PROTOTYPES = {
     "knn_tmp_bytes": (_SZ, [_I32]),
     "knn_mean_dist2": (C.c_int, [_P, _I32, _P, _P, _SZ, _P]),
     "knn_mean_dist2_idx": (C.c_int, [_P, _I32, _P, _P, _P, _SZ, _P]),
+    "grid_encode_tmp_bytes": (_SZ, [_I64, _I32, _I32, _I32, _I64]),
+    "grid_encode_fwd": (C.c_int, [_P, _I64, _I32, _P, _I64, _I32, _P, _I32, _F, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "grid_encode_bwd": (C.c_int, [_P, _P, _I64, _I32, _I64, _I32, _P, _I32, _F, _I32, _I32, _I32, _I32, _P, _P, _P, _P,
+                                  _SZ, _P]),
+    "sh_encode_fwd": (C.c_int, [_P, _I64, _I32, _P, _P]),
+    "sh_encode_bwd": (C.c_int, [_P, _P, _I64, _I32, _P, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -219,7 +225,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # the image stage (exposure, clamp, alpha mask) and the exposures' Adam: the oracle restates them in torch
                "image_stage_partials_count", "image_stage_fwd", "image_stage_bwd", "exposure_adam",
                # the criterion without its clamped image: a fusion of kernels the checker has, compared against them on the GPU
-               "lgdwt_fused_fwd", "lgdwt_fused_bwd")
+               "lgdwt_fused_fwd", "lgdwt_fused_bwd",
+               # DNGaussian's grid / SH encoders: the oracle restates them in torch (tests/encoding_reference.py)
+               "grid_encode_tmp_bytes", "grid_encode_fwd", "grid_encode_bwd", "sh_encode_fwd", "sh_encode_bwd")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 
