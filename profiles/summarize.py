@@ -42,7 +42,7 @@ OURS = ("preprocess_fwd_kernel", "scan_block_sums_kernel", "rs_hist_kernel", "rs
         "status_tag_kernel", "rs_small_sort_kernel", "step_uninstanced_kernel", "chain_kernel",
         "tb_entries_kernel", "tb_emit_kernel", "tb_regions_from_counts_kernel", "tb_regions_kernel", "tb_tile_count_kernel",
         "tb_region_scan_kernel", "tb_tile_scan_kernel", "tb_write_kernel", "depth_l1_kernel", "rows_pack_kernel", "row_mask_kernel",
-        "ssim_fwd_clamp_kernel", "lgdwt_bwd_kernel")
+        "ssim_fwd_clamp_kernel", "lgdwt_bwd_kernel", "lgdwt_fwd_kernel")
 
 
 def short(name):
@@ -125,7 +125,8 @@ stage_of = {"render_bwd": "render_bwd_wave_kernel", "render_fwd": "render_fwd_wa
             "duplicate": "duplicate_kernel", "tile_ranges": "tile_ranges_kernel", "region_bin": "region_bin_kernel",
             "ssim_fwd": "ssim_fwd_kernel", "ssim_bwd": "ssim_bwd_kernel",
             "step_uninstanced": "step_uninstanced_kernel", "chain": "chain_kernel"}
-for st, kn in (("ssim_fwd", "ssim_fwd_clamp_kernel"), ("ssim_bwd", "lgdwt_bwd_kernel")):
+# (later pairs win: lgdwt_fwd_kernel is the forward's one launch, ssim_fwd_clamp_kernel its two-launch form's second)
+for st, kn in (("ssim_fwd", "ssim_fwd_clamp_kernel"), ("ssim_fwd", "lgdwt_fwd_kernel"), ("ssim_bwd", "lgdwt_bwd_kernel")):
     if kn in traffic:   # the criterion without its clamped image (gs_lgdwt_fused_fwd / _bwd) times under the SSIM stages
         stage_of[st] = kn
 out = {st: traffic[k] for st, k in stage_of.items() if k in traffic}

@@ -17,7 +17,7 @@ enum GsStage {
   ST_PREPROCESS_BWD,
   ST_KNN,
   ST_L1,
-  ST_DWT2_FWD,
+  ST_DWT2_FWD,  // (no launches where gs_lgdwt_fused_fwd issues its one launch: that one times under ST_SSIM_FWD)
   ST_DWT2_BWD,
   ST_SSIM_FWD,
   ST_SSIM_BWD,
