@@ -455,6 +455,9 @@ class RasterBackend:
     # (kind "geom", "img", "binning"), so that a test decides what the buffer holds before the forward runs instead of the
     # caching allocator (tests/test_gpu_scratch_reuse.py); None: nothing happens
     scratch_fill = None
+    # test hook: called as output_fill(kind, tensor) for each output tensor of rasterize_gaussians ("color", "invdepth", "radii",
+    # "extra") before any kernel runs, so that a test can plant a pattern and see an element nobody wrote; None: nothing happens
+    output_fill = None
     KEYED_LIMITS = os.environ.get("GS_KEYED_LIMITS", "1") != "0"
     # region-binned forwards whose verdict is collected later (deferred eager steps, replayed graphs): the status block is
     # written into the pinned host block by the forward's own last kernel (GsScratch.status_host) instead of by a copy
@@ -542,6 +545,10 @@ class RasterBackend:
         radii = alloc((P,), dtype=torch.int32, device=device)
         out_extra = None if (extra is None and not fsgs) else alloc((1, H, W), **f32)
         tail = () if out_extra is None else (out_extra,)
+        if self.output_fill is not None and P != 0:
+            for kind, t in (("color", out_color), ("invdepth", out_invdepth), ("radii", radii), ("extra", out_extra)):
+                if t is not None:
+                    self.output_fill(kind, t)
         # (the one-shot requests of this forward are taken here, whatever follows: an empty model must not leave them armed)
         raw, self.raw_activations = self.raw_activations, False
         sh_rest, self.sh_rest = self.sh_rest, None

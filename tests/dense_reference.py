@@ -4,7 +4,18 @@ Written from the math, not from the oracle: every pixel evaluates every Gaussian
 for the skip rules, a global depth sort gives the blend order, exclusive cumulative products give
 the transmittance, and torch autograd supplies all parameter gradients.  Integer decisions that are
 not differentiable (radius, tile rectangle, visibility) are taken from the same closed-form rules
-(forward.cu:179-268) evaluated here in float64.  Feasible for P <= ~300 and <= 64x64 images.
+(forward.cu:179-268) evaluated here in float64.
+
+Two gradients are NOT the derivative of the forward expression but the reference's own convention, reproduced because the
+reference is the parity target (DESIGN.md section 2 lists them): the anti-aliasing factor (_AAScale) and the 0.99 clamp of
+alpha, which the reference's backward differentiates as if it were not there.  On those two the model is not independent
+of the oracle and the kernels: they share the convention by construction, and a test that exercises them (the opacity-1
+cases of tests/blend_cases.py) checks that all three apply it the same way, not that it is the right derivative.
+
+Cost: about 30 [N pixels, G visible Gaussians] float64 tensors stay alive for autograd, i.e. 240 N G bytes: 1 300
+Gaussians on a 64x64 image (tests/blend_cases.py's largest allowance) take 1.3 GB and a few seconds, a 16x16 image with
+the same list 80 MB.  That is the limit the constructed scenes were built within; nothing here is chunked, so ten times
+the pairs (13 GB) is out of reach on a test machine.
 """
 import math
 
@@ -67,8 +78,11 @@ class _AAScale(torch.autograd.Function):
             w * (w * x + x * x + z * z) * denom_f
 
 
-def render(scene, cam, bg, antialiasing=False, want_invdepth=True):
-    """scene tensors must be float64 leaves (requires_grad as desired).  Returns dict."""
+def render(scene, cam, bg, antialiasing=False, want_invdepth=True, detail=False):
+    """scene tensors must be float64 leaves (requires_grad as desired).  Returns dict.
+    detail: also return, detached, what every (pixel, entry) pair went through (tests/blend_cases.py's margin condition):
+    order [G] (Gaussian id of column g), in_rect / power / raw = opacity exp(power) [N, G], tested [N, G] (the pixel was
+    still alive and the entry passed the skip rules: the saturation test ran) and test_T [N, G] (T (1 - alpha) there)."""
     f64 = torch.float64
     means = scene["means3D"]
     P = means.shape[0]
@@ -163,12 +177,17 @@ def render(scene, cam, bg, antialiasing=False, want_invdepth=True):
     power = -0.5 * (cn[:, 0][None] * dx * dx + cn[:, 2][None] * dy * dy) - cn[:, 1][None] * dx * dy
     in_rect = (tile_x[:, None] >= rminx[o][None]) & (tile_x[:, None] < rmaxx[o][None]) & \
               (tile_y[:, None] >= rminy[o][None]) & (tile_y[:, None] < rmaxy[o][None])
-    alpha = torch.clamp_max(opac[o][None] * torch.exp(power), 0.99)
+    raw = opac[o][None] * torch.exp(power)
+    # the reference's backward recomputes alpha = min(0.99, o G) and then differentiates o G as if the clamp were not
+    # there (backward.cu:569, 619, 635: dL_dG = o dL_dalpha, dL_dopacity += G dL_dalpha, clamped or not): the parity
+    # target's gradient passes straight through the clamp, where autograd's clamp_max would give zero
+    alpha = raw + (torch.clamp_max(raw, 0.99) - raw).detach()
     live = in_rect & (power <= 0) & (alpha >= 1.0 / 255.0)
     alpha = torch.where(live, alpha, torch.zeros_like(alpha))
     Tinc = torch.cumprod(1 - alpha, dim=1)
     stop = live & (Tinc < 0.0001)
     dead = torch.cumsum(stop.to(torch.int64), dim=1) > 0       # the stopping Gaussian itself is not blended
+    test_T, tested = Tinc.detach(), live & ~(dead & ~(stop & (torch.cumsum(stop.to(torch.int64), dim=1) == 1)))
     alpha = torch.where(dead, torch.zeros_like(alpha), alpha)
     Tinc = torch.cumprod(1 - alpha, dim=1)
     Texc = torch.cat([torch.ones((alpha.shape[0], 1), dtype=f64), Tinc[:, :-1]], dim=1)
@@ -184,6 +203,12 @@ def render(scene, cam, bg, antialiasing=False, want_invdepth=True):
     blended = (alpha > 0)
     n_contrib = torch.where(blended, pos_in_tile, torch.zeros_like(pos_in_tile)).max(dim=1).values \
         if alpha.shape[1] > 0 else torch.zeros(alpha.shape[0], dtype=torch.int64)
-    return dict(color=color.t().reshape(3, H, W), invdepth=invd.reshape(1, H, W), radii=radii,
+    last = torch.where(blended, pos_in_tile, torch.zeros_like(pos_in_tile)).argmax(dim=1) if alpha.shape[1] > 0 else n_contrib
+    last_id = torch.where(n_contrib > 0, o[last] if alpha.shape[1] > 0 else n_contrib, torch.full_like(n_contrib, -1))
+    extra = {}
+    if detail:
+        extra["detail"] = dict(order=o, in_rect=in_rect, power=power.detach(), raw=raw.detach(), tested=tested, test_T=test_T,
+                               tile_len=in_rect.to(torch.int64).sum(dim=1).reshape(H, W))
+    return dict(last_id=last_id.reshape(H, W), **extra, color=color.t().reshape(3, H, W), invdepth=invd.reshape(1, H, W), radii=radii,
                 depth=depth.reshape(1, H, W), alpha=alpha_img.reshape(1, H, W),
                 final_T=T_final.reshape(H, W), n_contrib=n_contrib.reshape(H, W), means2D=torch.stack([px, py], 1))
