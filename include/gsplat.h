@@ -502,6 +502,40 @@ int gs_grid_encode_bwd(const float* grad, const float* inputs, int64_t B, int32_
 int gs_sh_encode_fwd(const float* inputs, int64_t B, int32_t degree, float* outputs, void* stream);
 int gs_sh_encode_bwd(const float* grad, const float* inputs, int64_t B, int32_t degree, float* grad_inputs, void* stream);
 
+/* ---- DNGaussian's depth-normalisation regulariser (utils/loss_utils.py: patch_norm_{mse,l1}_loss[_global],
+ * loss_depth_smoothness), fp32, one [1,1,H,W] image ----
+ * Patches: non-overlapping p x p (2 <= p <= min(H, W)), stride p, rows / columns beyond floor(H/p) p, floor(W/p) p dropped;
+ * L = floor(H/p) floor(W/p) patches in row-major patch order, elements row-major inside a patch (the order of mask_out).
+ * n(x) = (x - patch mean) / (s + 1e-2 std_all): std_all = unbiased std of the L p^2 patchified elements (carries gradient);
+ * s = the patch's unbiased std (carries gradient), or with GS_DN_GLOBAL the unbiased std of the whole uncropped image
+ * (detached).  d = n(input) - n(target), mask = |d| > margin; loss = mean over the mask of d^2 (GS_DN_L1: |d|): NaN on an
+ * empty mask, and then a zero gradient.  The gradient goes to input only.
+ * tmp: >= gs_depth_norm_tmp_bytes(H, W, p_local, p_global) bytes of device scratch (0 = that term is absent); a single-loss
+ * call sizes it with (p, 0) whatever its form, the smoothness pair with (0, 0).  The forward leaves in tmp what the backward
+ * of the SAME arguments reads; the backward is one launch and reads dL/dloss from device memory (no host synchronisation
+ * anywhere, every sum in one fixed order: the same bits on every run).
+ * gs_depth_smooth_*: loss = (sum |dx depth| wx + sum |dy depth| wy) / (sum wx + sum wy), wx = exp(-mean_c |dx img|), img [C,H,W].
+ * gs_dng_depth_reg_*: the reference's call in one pass structure: w_local * mse(p_local) + w_smooth * smoothness(input,
+ * target) + w_global * mse_global(p_global), both with `margin`; loss_out[4] = total, local, global, smoothness (0 when
+ * w_smooth == 0: the term is skipped); mask_local / mask_global nullable. */
+#define GS_DN_GLOBAL 1
+#define GS_DN_L1 2
+size_t gs_depth_norm_tmp_bytes(int32_t H, int32_t W, int32_t p_local, int32_t p_global);
+int gs_depth_norm_fwd(const float* input, const float* target, int32_t H, int32_t W, int32_t p, float margin, int32_t flags,
+                      void* tmp, float* loss_out, uint8_t* mask_out /*[L p^2] or NULL*/, void* stream);
+int gs_depth_norm_bwd(const float* input, const float* target, int32_t H, int32_t W, int32_t p, float margin, int32_t flags,
+                      const void* tmp, const float* dloss_dev, float* grad_input /*[H,W]*/, void* stream);
+int gs_depth_smooth_fwd(const float* depth, const float* img, int32_t C, int32_t H, int32_t W, void* tmp, float* loss_out,
+                        void* stream);
+int gs_depth_smooth_bwd(const float* depth, const float* img, int32_t C, int32_t H, int32_t W, const void* tmp,
+                        const float* dloss_dev, float* grad_depth /*[H,W]*/, void* stream);
+int gs_dng_depth_reg_fwd(const float* input, const float* target, int32_t H, int32_t W, int32_t p_local, int32_t p_global,
+                         float margin, float w_local, float w_global, float w_smooth, void* tmp, float* loss_out /*[4]*/,
+                         uint8_t* mask_local, uint8_t* mask_global, void* stream);
+int gs_dng_depth_reg_bwd(const float* input, const float* target, int32_t H, int32_t W, int32_t p_local, int32_t p_global,
+                         float margin, float w_local, float w_global, float w_smooth, const void* tmp, const float* dloss_dev,
+                         float* grad_input /*[H,W]*/, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).
