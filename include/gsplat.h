@@ -536,6 +536,32 @@ int gs_dng_depth_reg_bwd(const float* input, const float* target, int32_t H, int
                          float margin, float w_local, float w_global, float w_smooth, const void* tmp, const float* dloss_dev,
                          float* grad_input /*[H,W]*/, void* stream);
 
+/* ---- FSGS's depth-correlation term (FSGS/train.py:100-109,121-131; csrc/gs_pearson.hip) ----
+ * Pearson's r of two fp32 sequences of n >= 2 elements, r = Sxy / sqrt(Sxx Syy) clamped to [-1, 1], and the loss 1 - r.  The
+ * second sequence is derived from the target t inside the kernel by a FORM: y = t (ID), -t (NEG), 1 / (t + 200) in fp32
+ * (RECIP200).  A forward serves form_a and, unless form_b is -1, form_b from one read of x and t, and picks the branch on the
+ * device by the rule of Python's min(loss_a, loss_b): b only if loss_b < loss_a, so a tie or a NaN keeps a.
+ * out[4] = loss of the chosen form, its r, loss_a, loss_b (NaN without form_b); branch_out (nullable) = 0 / 1.
+ * A constant sequence (Sxx or Syy = 0) gives a NaN loss and zero gradients.
+ * tmp: >= gs_pearson_tmp_bytes(n) bytes of device scratch (0: n out of range).  The forward (two launches) leaves in tmp what the
+ * backward of the SAME arguments reads.  The backward is one launch: dout_dev is dL/dloss of the chosen form, or dL/dr with
+ * GS_PEARSON_WRT_R, read from device memory; grad_x and grad_t are each nullable, not both; the gradient to t goes through
+ * the form's derivative and exists for ID and NEG only (GS_E_UNSUPPORTED with RECIP200).  The clamp does not gate the gradient.
+ * No host synchronisation anywhere and every sum in one fixed order: the same bits on every run.  The sums are float64 sums of
+ * the values shifted by the sequences' first elements.  A workgroup sweeps GS_PEARSON_BLOCK_ELEMS elements at a time, the grid
+ * is at most GS_PEARSON_MAX_BLOCKS workgroups and strides over what is left. */
+#define GS_PEARSON_ID 0
+#define GS_PEARSON_NEG 1
+#define GS_PEARSON_RECIP200 2
+#define GS_PEARSON_WRT_R 1
+#define GS_PEARSON_BLOCK_ELEMS 4096
+#define GS_PEARSON_MAX_BLOCKS 512
+size_t gs_pearson_tmp_bytes(int64_t n);
+int gs_pearson_fwd(const float* x, const float* t, int64_t n, int32_t form_a, int32_t form_b /* -1: none */, void* tmp,
+                   float* out /*[4]*/, int32_t* branch_out, void* stream);
+int gs_pearson_bwd(const float* x, const float* t, int64_t n, int32_t form_a, int32_t form_b, int32_t flags, const void* tmp,
+                   const float* dout_dev, float* grad_x /*[n]*/, float* grad_t /*[n]*/, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

@@ -170,6 +170,9 @@ PROTOTYPES = {
     "depth_smooth_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "dng_depth_reg_fwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P, _P, _P, _P]),
     "dng_depth_reg_bwd": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _F, _F, _F, _P, _P, _P, _P]),
+    "pearson_tmp_bytes": (_SZ, [_I64]),
+    "pearson_fwd": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
+    "pearson_bwd": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -237,7 +240,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                "grid_encode_tmp_bytes", "grid_encode_fwd", "grid_encode_bwd", "sh_encode_fwd", "sh_encode_bwd",
                # DNGaussian's depth-normalisation losses: restated in torch (tests/dng_depth_reference.py)
                "depth_norm_tmp_bytes", "depth_norm_fwd", "depth_norm_bwd", "depth_smooth_fwd", "depth_smooth_bwd",
-               "dng_depth_reg_fwd", "dng_depth_reg_bwd")
+               "dng_depth_reg_fwd", "dng_depth_reg_bwd",
+               # FSGS's Pearson depth loss: restated in torch (tests/fsgs_loss_reference.py)
+               "pearson_tmp_bytes", "pearson_fwd", "pearson_bwd")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

@@ -678,6 +678,41 @@ class GaussianModelLite:
             self.max_radii2D = torch.zeros((self.P,), device=self.device)
             return int(ci.numel()), ns, int(prune.sum())
 
+    def proximity(self, extent, api=None):
+        """FSGS's proximity-guided unpooling (FSGS/scene/gaussian_model.py:405-420, N = 3), the reference's tensor
+        expressions one for one: a Gaussian is selected if its mean SQUARED distance to its three nearest neighbours
+        exceeds 5 * extent (a length - the reference compares the two as they are) and its largest activated scale exceeds
+        extent; every selected Gaussian adds three: raw scaling and raw opacity of the neighbour, rotation (1, 0, 0, 0), zero
+        SH.  New row j takes neighbour j of the flattened [S, 3] neighbour lists (selected Gaussian j // 3, nearest first) and
+        lies midway between that neighbour and selected Gaussian j % S: the reference's `_xyz[mask].repeat(1, N, 1)` TILES the
+        S selected rows, it does not repeat each three times, so only with S = 1 is every new Gaussian between a Gaussian
+        and its own neighbour.  Reproduced as written.
+        The new rows follow the existing ones (whose parameters and Adam moments stay, new moments are zero), the statistics
+        are zeroed at the new size (densification_postfix) and the spatial order is restored as densify_and_prune does.
+        api: whose kNN to use (default: the optimizer's).  Returns the number of new rows."""
+        if self.with_nir:
+            raise NotImplementedError("proximity: the multispectral model has no rule for the new rows' NIR albedo")
+        from .knn import dist2_with_indices
+        with torch.no_grad():
+            P0 = self.P
+            raw = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
+            dist, nearest = dist2_with_indices(api or self.optimizer.api, raw["xyz"])
+            sel = torch.logical_and(dist > (5. * extent), torch.max(self.get_scaling, dim=1).values > extent)
+            new_idx = nearest[sel].reshape(-1).long()
+            source_xyz = raw["xyz"][sel].repeat(1, 3, 1).reshape(-1, 3)
+            new = {"xyz": (source_xyz + raw["xyz"][new_idx]) / 2, "scaling": raw["scaling"][new_idx],
+                   "opacity": raw["opacity"][new_idx], "features": torch.zeros_like(raw["features"][new_idx])}
+            new["rotation"] = torch.zeros_like(raw["rotation"][new_idx])
+            new["rotation"][:, 0] = 1
+            self._relayout(torch.arange(P0, device=raw["xyz"].device), new)
+            if getattr(self, "spatial_order", False):
+                from . import synthetic
+                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
+            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+            self.denom = torch.zeros((self.P, 1), device=self.device)
+            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            return int(new_idx.numel())
+
     def reset_opacity(self):
         """gaussian_model.py:258-261: opacity <- min(opacity, 0.01), moments of that group zeroed."""
         with torch.no_grad():
