@@ -269,6 +269,13 @@ int gs_backward_fsgs(const GsView* view, const GsGaussians* g, const int32_t* ra
 int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix,
                     const float* projmatrix, uint8_t* present, void* stream);
 
+/* Region binning (GsView.tile_cull = 2), which form of the forward geometry kernel fills the region buckets: 1 = a wave shares
+ * the regions of its large footprints among its lanes (csrc/gs_preprocess.hip), 0 = every lane walks its own.  Same lists,
+ * same records, bit for bit; the second form is the control arm of a measurement.  form < 0 changes nothing.  Returns the
+ * form the next launches take; until set it is the environment's GS_REGION_COOP (read once), else the built-in default.
+ * Not synchronised with launches in flight on other threads. */
+int gs_region_coop(int32_t form);
+
 /* ---- debug / parity exports: copy internal state into plain arrays (any pointer may be
  * NULL).  Used by the parity tests to compare against the oracle; not on the hot path. ---- */
 int gs_export_geom(const GsScratch* scratch, int32_t P, float* depths, float* means2D /*[P,2]*/,

@@ -73,6 +73,23 @@ static inline size_t preprocess_limit_lds_floats(const PreprocessArgs& a) {
   return want <= GS_LIMIT_LDS_MAX_FLOATS ? want : 0;
 }
 
+// Region mode, cooperative form (COOP, launched with tile_cull == 2 only): what a wave shares of its large footprints.
+// One lane's descriptor of a footprint of more than four regions, and the wave's running sum of their sizes.
+#ifndef GS_REGION_COOP_DEFAULT
+#define GS_REGION_COOP_DEFAULT 1
+#endif
+// (region, Gaussian) pairs a lane has in flight per round: a round is 64 * GS_COOP_PAIRS pairs.  (4 - 94 VGPRs instead of
+// 90 - measured the same step at C3: 0.846 ms both.)
+#define GS_COOP_PAIRS 2
+struct CoopWave {
+  uint32_t pref[64];   // inclusive prefix of the published region counts (0 for a lane that published nothing)
+  uint32_t dbits[64];  // depth bits of the lane's Gaussian
+  uint32_t r0[64];     // first region: rx0 | ry0 << 16
+  uint32_t nrx[64];    // regions per row of the rectangle
+  uint32_t tiles[64];  // with depth limits: accepted regions
+};
+
+template <bool COOP>
 __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs a, GeomView g, int lds_floats) {
   const int idx = blockIdx.x * GS_BLOCK + threadIdx.x;
   uint32_t tiles = 0, entries = TB_ENTRIES_UNKNOWN;
@@ -135,16 +152,119 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
                "+v"(rq_in.w));
   const GsLdsFloatPtr lds_seg = (GsLdsFloatPtr)s_limit + (GS_LIMIT_TILES_IN_LDS ? T : 0);
   if (idx == 0) g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
+  // region mode: the bound of region (rx, ry) = the largest of its (up to) four row-segment bounds: a pair within its TILE's
+  // bound lies in a region it is not beyond
+  const int segs_x = (int)depth_limit_segs_x((uint32_t)a.grid_x);
+  auto region_bound = [&](int rx, int ry) {
+    float bound = -__builtin_inff();
+#pragma unroll
+    for (int k = 0; k < RG_TILES; k++) {
+      const int ty = min(ry * RG_TILES + k, a.grid_y - 1);
+      const float v = lds_floats ? lds_seg[ty * segs_x + rx] : a.tile_depth_limit[(size_t)T + ty * segs_x + rx];
+      bound = fmaxf(bound, v);
+    }
+    return bound;
+  };
+  Splat sp;
+  sp.x = sp.y = sp.depth = sp.invdepth = 0.f;
+  sp.cxx = sp.cxy = sp.cyy = sp.opacity = 0.f;
+  sp.r = sp.g = sp.b = 0.f;
+  sp.extra = 0.f;
+  int radius_out = 0;
+  sp.rect_min = sp.rect_max = sp.tiles = sp.clamped = 0;
+  float cov3D[6] = {0, 0, 0, 0, 0, 0};
+  bool write_cov = false;
+  // COOP: the Gaussian passed every cull - its verdict and colour (`finish`) follow the wave's cooperative part -, and the
+  // footprint of more than four regions it publishes there: size, first region (rx0 | ry0 << 16), regions per row
+  bool reached = false;
+  uint32_t big_n = 0, big_r0 = 0, big_nrx = 0;
+
+  // What follows the tile stage: the entry count, the colour and `sp.tiles`.
+  auto finish = [&]() {
+    // bits 16-31 of `clamped`: region entries of this Gaussian (bit 15 of them: row-wise enumeration), TB_ENTRIES_UNKNOWN when
+    // the binning has to count for itself
+    sp.clamped |= (tiles ? entries : 0u) << 16;
+    // the colour comes last: a Gaussian whose every pair the depth limits removed is blended nowhere, so its 192 B of SH
+    // coefficients are neither read nor evaluated (its gradient is zero as well, see preprocess_bwd)
+    if (!(a.tile_depth_limit && tiles == 0)) {
+      if (a.colors_precomp == nullptr) {
+        V3 campos = {cam[0], cam[1], cam[2]};
+        V3 rgb;
+        uint32_t cl = 0;
+        if (a.M == 16 && a.shs_rest) {
+          // the model's split rows (GsGaussians.shs_rest): 12 B of _features_dc + the active part of the 180 B row of
+          // _features_rest, dword loads (a 180 B row starts on a 16 B boundary for every fourth Gaussian only)
+          ShRegs sh;
+          const float* dc = a.shs + (size_t)idx * 3;
+          const float* rest = a.shs_rest + (size_t)idx * 45;
+          const int nfl = 3 * (a.D + 1) * (a.D + 1) - 3;
+          sh.f[0] = dc[0]; sh.f[1] = dc[1]; sh.f[2] = dc[2];
+#pragma unroll
+          for (int k = 0; k < 45; k++) sh.f[3 + k] = k < nfl ? rest[k] : 0.f;
+          bump();
+          rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
+        } else if (a.M == 16) {
+          ShRegs sh;
+          const float4* src = reinterpret_cast<const float4*>(a.shs + (size_t)idx * 48);
+          const int nvec = a.D == 0 ? 1 : (a.D == 1 ? 3 : (a.D == 2 ? 7 : 12));
+#pragma unroll
+          for (int k = 0; k < 12; k++) {
+            if (k < nvec) {
+              float4 v = src[k];
+              sh.f[4 * k] = v.x; sh.f[4 * k + 1] = v.y; sh.f[4 * k + 2] = v.z; sh.f[4 * k + 3] = v.w;
+            } else {
+              sh.f[4 * k] = sh.f[4 * k + 1] = sh.f[4 * k + 2] = sh.f[4 * k + 3] = 0.f;
+            }
+          }
+          bump();
+          rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
+        } else if (a.shs_rest) {
+          bump();
+          ShMemSplit sh{a.shs + (size_t)idx * 3, a.shs_rest + (size_t)idx * (a.M - 1) * 3};
+          rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
+        } else {
+          bump();
+          ShMem sh{a.shs + (size_t)idx * a.M * 3};
+          rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
+        }
+        sp.r = rgb.x; sp.g = rgb.y; sp.b = rgb.z;
+        sp.clamped |= cl;  // (bits 8-9 already hold the depth-limit verdict)
+      } else {
+        bump();
+        sp.r = a.colors_precomp[3 * idx];
+        sp.g = a.colors_precomp[3 * idx + 1];
+        sp.b = a.colors_precomp[3 * idx + 2];
+      }
+    }
+    sp.tiles = tiles;
+  };
+
+  // a Gaussian the depth limits removed entirely leaves no record and no covariance behind: nothing downstream reads
+  // them (its depth key is 0xFFFFFFFF, so it is not in the depth order - n_ordered counts the other keys at both sort sizes -,
+  // no list names it, the backward skips it on tiles_touched == 0, and gs_export_geom reports it as invisible: see
+  // HDR_LIMITED)
+  bool write_record = true;
+  auto store_record = [&](int half) {  // 0: mean, depth, conic, opacity; 1: colour, extra, rectangle, tiles, flags
+    float4* dst = reinterpret_cast<float4*>(&g.splat[idx]);
+    const float4* srcv = reinterpret_cast<const float4*>(&sp);
+    dst[2 * half] = srcv[2 * half]; dst[2 * half + 1] = srcv[2 * half + 1];
+  };
+  // everything but the record's second half: needs the final `tiles`, not the colour
+  auto store_geometry = [&]() {
+    write_record = !(a.tile_depth_limit && tiles == 0 && radius_out > 0);
+    if (write_record) store_record(0);
+    if (a.cov3D_precomp == nullptr && write_record) {
+      float2* cd = reinterpret_cast<float2*>(g.cov3D + (size_t)idx * 6);
+      if (!write_cov) { cov3D[0] = cov3D[1] = cov3D[2] = cov3D[3] = cov3D[4] = cov3D[5] = 0.f; }
+      cd[0] = make_float2(cov3D[0], cov3D[1]);
+      cd[1] = make_float2(cov3D[2], cov3D[3]);
+      cd[2] = make_float2(cov3D[4], cov3D[5]);
+    }
+    g.tiles_touched[idx] = tiles;
+    a.radii[idx] = radius_out;
+  };
+
   if (idx < a.P) {
-    Splat sp;
-    sp.x = sp.y = sp.depth = sp.invdepth = 0.f;
-    sp.cxx = sp.cxy = sp.cyy = sp.opacity = 0.f;
-    sp.r = sp.g = sp.b = 0.f;
-    sp.extra = 0.f;
-    int radius_out = 0;
-    sp.rect_min = sp.rect_max = sp.tiles = sp.clamped = 0;
-    float cov3D[6] = {0, 0, 0, 0, 0, 0};
-    bool write_cov = false;
     do {
       // in_frustum, auxiliary.h:151-176
       V3 p_view = xform4x3(p_orig, vm);
@@ -212,7 +332,7 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
       sp.opacity = activate_opacity(op_in, a.raw_activations) * h_convolution_scaling;
       sp.rect_min = minx | (miny << 16);
       sp.rect_max = maxx | (maxy << 16);
-      if (a.tile_cull == 2) {
+      if (COOP || a.tile_cull == 2) {
         // Region binning (gs_regionbin.hip): into the bucket of every 4 x 4-tile region that the bounding box of the
         // alpha >= 1/255 ellipse reaches (inside the reference rectangle) and, with depth limits, whose largest tile bound the
         // Gaussian is not beyond.  `tiles` counts the regions: non-zero = "may have instances" for everything downstream.
@@ -229,36 +349,34 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
             ty1 = min(ty1, (int)floorf(yh * 0.0625f) + 1);
           }
           if (tx1 > tx0 && ty1 > ty0) {
-            const int segs_x = (int)depth_limit_segs_x((uint32_t)a.grid_x);
             // A returning device-scope atomic is the slowest thing this kernel does (about 5 us under load at C3; measured: a
             // second set of them costs 16 us of the kernel's 120).  So: never one after the other - the bucket counters of a
             // Gaussian are bumped four at a time, back to back (a footprint within 2 x 2 regions, nearly all of them, has one
             // such batch; taking the regions beyond the fourth one by one cost 29 us, the wave waiting for its largest
             // Gaussian) - and the last batch is issued behind the loads of the SH row and collected after the colour is
             // computed, so that its round trip hides under that of the coefficients (`bump` / `collect` below).
+            // !COOP: a lane walks all of its rectangle, a batch of four after the other - the wave waits for its largest
+            // Gaussian's chain of round trips.  COOP: a rectangle of more than four regions is published instead and the
+            // wave's lanes share the pairs of all of them (below).
             dbits = __float_as_uint(sp.depth);
-            for (int ry = ty0 >> 2; ry <= (ty1 - 1) >> 2; ry++) {
-              for (int rx = tx0 >> 2; rx <= (tx1 - 1) >> 2; rx++) {
-                if (a.tile_depth_limit) {
-                  // the region's bound = the largest of its (up to) four row-segment bounds: a pair within its TILE's
-                  // bound lies in a region it is not beyond
-                  float bound = -__builtin_inff();
-#pragma unroll
-                  for (int k = 0; k < RG_TILES; k++) {
-                    const int ty = min(ry * RG_TILES + k, a.grid_y - 1);
-                    const float v = lds_floats ? lds_seg[ty * segs_x + rx] : a.tile_depth_limit[(size_t)T + ty * segs_x + rx];
-                    bound = fmaxf(bound, v);
-                  }
-                  if (depth_beyond_limit(sp.depth, bound)) continue;
+            const int rx0 = tx0 >> 2, rx1 = (tx1 - 1) >> 2, ry0 = ty0 >> 2, ry1 = (ty1 - 1) >> 2;
+            if (COOP && (rx1 - rx0 + 1) * (ry1 - ry0 + 1) > 4) {
+              big_nrx = (uint32_t)(rx1 - rx0 + 1);
+              big_n = big_nrx * (uint32_t)(ry1 - ry0 + 1);
+              big_r0 = (uint32_t)rx0 | (uint32_t)ry0 << 16;
+            } else {
+              for (int ry = ry0; ry <= ry1; ry++) {
+                for (int rx = rx0; rx <= rx1; rx++) {
+                  if (a.tile_depth_limit && depth_beyond_limit(sp.depth, region_bound(rx, ry))) continue;
+                  const int r = ry * a.rg_x + rx;
+                  tiles++;
+                  if (!COOP && n_pend == 4) { bump(); collect(); }
+                  p0 = n_pend == 0 ? r : p0;
+                  p1 = n_pend == 1 ? r : p1;
+                  p2 = n_pend == 2 ? r : p2;
+                  p3 = n_pend == 3 ? r : p3;
+                  n_pend++;
                 }
-                const int r = ry * a.rg_x + rx;
-                tiles++;
-                if (n_pend == 4) { bump(); collect(); }
-                p0 = n_pend == 0 ? r : p0;
-                p1 = n_pend == 1 ? r : p1;
-                p2 = n_pend == 2 ? r : p2;
-                p3 = n_pend == 3 ? r : p3;
-                n_pend++;
               }
             }
           }
@@ -333,87 +451,112 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
         tiles = (maxy - miny) * (maxx - minx);
         entries = tb_rect_entries(minx, miny, maxx, maxy);
       }
-      // bits 16-31 of `clamped`: region entries of this Gaussian (bit 15 of them: row-wise enumeration), TB_ENTRIES_UNKNOWN when
-      // the binning has to count for itself
-      sp.clamped |= (tiles ? entries : 0u) << 16;
-      // the colour comes last: a Gaussian whose every pair the depth limits removed is blended nowhere, so its 192 B of SH
-      // coefficients are neither read nor evaluated (its gradient is zero as well, see preprocess_bwd)
-      if (!(a.tile_depth_limit && tiles == 0)) {
-        if (a.colors_precomp == nullptr) {
-          V3 campos = {cam[0], cam[1], cam[2]};
-          V3 rgb;
-          uint32_t cl = 0;
-          if (a.M == 16 && a.shs_rest) {
-            // the model's split rows (GsGaussians.shs_rest): 12 B of _features_dc + the active part of the 180 B row of
-            // _features_rest, dword loads (a 180 B row starts on a 16 B boundary for every fourth Gaussian only)
-            ShRegs sh;
-            const float* dc = a.shs + (size_t)idx * 3;
-            const float* rest = a.shs_rest + (size_t)idx * 45;
-            const int nfl = 3 * (a.D + 1) * (a.D + 1) - 3;
-            sh.f[0] = dc[0]; sh.f[1] = dc[1]; sh.f[2] = dc[2];
-  #pragma unroll
-            for (int k = 0; k < 45; k++) sh.f[3 + k] = k < nfl ? rest[k] : 0.f;
-            bump();
-            rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
-          } else if (a.M == 16) {
-            ShRegs sh;
-            const float4* src = reinterpret_cast<const float4*>(a.shs + (size_t)idx * 48);
-            const int nvec = a.D == 0 ? 1 : (a.D == 1 ? 3 : (a.D == 2 ? 7 : 12));
-  #pragma unroll
-            for (int k = 0; k < 12; k++) {
-              if (k < nvec) {
-                float4 v = src[k];
-                sh.f[4 * k] = v.x; sh.f[4 * k + 1] = v.y; sh.f[4 * k + 2] = v.z; sh.f[4 * k + 3] = v.w;
-              } else {
-                sh.f[4 * k] = sh.f[4 * k + 1] = sh.f[4 * k + 2] = sh.f[4 * k + 3] = 0.f;
-              }
-            }
-            bump();
-            rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
-          } else if (a.shs_rest) {
-            bump();
-            ShMemSplit sh{a.shs + (size_t)idx * 3, a.shs_rest + (size_t)idx * (a.M - 1) * 3};
-            rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
-          } else {
-            bump();
-            ShMem sh{a.shs + (size_t)idx * a.M * 3};
-            rgb = color_from_sh(a.D, p_orig, campos, sh, cl);
-          }
-          sp.r = rgb.x; sp.g = rgb.y; sp.b = rgb.z;
-          sp.clamped |= cl;  // (bits 8-9 already hold the depth-limit verdict)
-        } else {
-          bump();
-          sp.r = a.colors_precomp[3 * idx];
-          sp.g = a.colors_precomp[3 * idx + 1];
-          sp.b = a.colors_precomp[3 * idx + 2];
-        }
+      if (COOP) {
+        reached = true;
+        break;
       }
-      sp.tiles = tiles;
+      finish();
     } while (false);
+  }
 
-    // a Gaussian the depth limits removed entirely leaves no record and no covariance behind: nothing downstream reads
-    // them (its depth key is 0xFFFFFFFF, so it is not in the depth order - n_ordered counts the other keys at both sort sizes -,
-    // no list names it, the backward skips it on tiles_touched == 0, and gs_export_geom reports it as invisible: see
-    // HDR_LIMITED)
-    const bool write_record = !(a.tile_depth_limit && tiles == 0 && radius_out > 0);
-    if (write_record) {
-      float4* dst = reinterpret_cast<float4*>(&g.splat[idx]);
-      const float4* srcv = reinterpret_cast<const float4*>(&sp);
-      dst[0] = srcv[0]; dst[1] = srcv[1]; dst[2] = srcv[2]; dst[3] = srcv[3];
+  // ---- COOP: the wave's large footprints, one (region, Gaussian) pair per lane.  Every lane of the wave is here - those past
+  // P, behind the camera or culled published nothing -, the wave's total is the same number in all of them, and nothing
+  // below waits for another wave: only wave-level ordering (LDS fence + wave barrier).
+  __shared__ CoopWave s_coop[COOP ? GS_BLOCK / 64 : 1];
+  CoopWave& cw = s_coop[COOP ? threadIdx.x >> 6 : 0];
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t coop_total = 0;
+  // the pairs a lane has in flight: region | owner lane << 26, and the slot its counter returned
+  uint32_t c_p[GS_COOP_PAIRS], c_s[GS_COOP_PAIRS];
+#pragma unroll
+  for (int j = 0; j < GS_COOP_PAIRS; j++) { c_p[j] = 0; c_s[j] = 0xFFFFFFFFu; }
+  auto wave_sync = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+  // pair k of the wave -> the lane that published it and its region; false: beyond the region's depth limit
+  auto coop_pair = [&](uint32_t k, uint32_t& owner, uint32_t& r) {
+    uint32_t o = 0;  // the first lane whose prefix is above k: the number of lanes whose prefix is not
+#pragma unroll
+    for (uint32_t step = 32; step; step >>= 1) o += cw.pref[o + step - 1u] <= k ? step : 0u;
+    const uint32_t local = k - (o ? cw.pref[o - 1u] : 0u), nrx = cw.nrx[o], r0 = cw.r0[o];
+    const uint32_t row = local / nrx;
+    const int rx = (int)((r0 & 0xFFFFu) + (local - row * nrx)), ry = (int)((r0 >> 16) + row);
+    owner = o;
+    r = (uint32_t)(ry * a.rg_x + rx);
+    return !(a.tile_depth_limit && depth_beyond_limit(__uint_as_float(cw.dbits[o]), region_bound(rx, ry)));
+  };
+  // one round: the counters of up to GS_COOP_PAIRS accepted pairs per lane bumped back to back, then their entries stored
+  auto coop_bump = [&](uint32_t base) {
+#pragma unroll
+    for (int j = 0; j < GS_COOP_PAIRS; j++) {
+      const uint32_t k = base + 64u * j + lane;
+      uint32_t o, r;
+      if (k < coop_total && coop_pair(k, o, r)) {
+        c_p[j] = r | o << 26;
+        c_s[j] = atomicAdd(&a.region_count[(size_t)r * RG_COUNT_STRIDE], 1u);
+      }
     }
-    if (a.cov3D_precomp == nullptr && write_record) {
-      float2* cd = reinterpret_cast<float2*>(g.cov3D + (size_t)idx * 6);
-      if (!write_cov) { cov3D[0] = cov3D[1] = cov3D[2] = cov3D[3] = cov3D[4] = cov3D[5] = 0.f; }
-      cd[0] = make_float2(cov3D[0], cov3D[1]);
-      cd[1] = make_float2(cov3D[2], cov3D[3]);
-      cd[2] = make_float2(cov3D[4], cov3D[5]);
+  };
+  auto coop_collect = [&]() {
+#pragma unroll
+    for (int j = 0; j < GS_COOP_PAIRS; j++) {
+      if (c_s[j] < a.region_cap) {
+        const uint32_t o = c_p[j] >> 26, r = c_p[j] & 0x3FFFFFFu;
+        a.region_bucket[(size_t)r * a.region_cap + c_s[j]] = make_uint2(cw.dbits[o], (uint32_t)idx - lane + o);
+      }
+      c_s[j] = 0xFFFFFFFFu;
     }
-    g.tiles_touched[idx] = tiles;
+  };
+  if constexpr (COOP) {
+    uint32_t pref = big_n;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t t = __shfl_up(pref, off, 64);
+      if ((int)lane >= off) pref += t;
+    }
+    coop_total = (uint32_t)__builtin_amdgcn_readlane((int)pref, 63);
+    if (coop_total) {
+      cw.pref[lane] = pref; cw.dbits[lane] = dbits; cw.r0[lane] = big_r0; cw.nrx[lane] = big_nrx; cw.tiles[lane] = 0;
+      wave_sync();
+      // acceptance first, without atomics: every lane learns its final `tiles`, so the "no record, no SH row when everything
+      // was cut" decision below is the one the per-lane form takes
+      if (a.tile_depth_limit) {
+        for (uint32_t base = 0; base < coop_total; base += 64u) {
+          const uint32_t k = base + lane;
+          uint32_t o, r;
+          if (k < coop_total && coop_pair(k, o, r)) atomicAdd(&cw.tiles[o], 1u);
+        }
+        wave_sync();
+        if (big_n) tiles = cw.tiles[lane];
+      } else {
+        tiles = big_n ? big_n : tiles;
+      }
+      // the rounds: all but the last wait for their slots here; the last one's round trip runs beside that of the SH rows
+      // requested next and is collected after the colour, like the lanes' own batches of up to four
+      uint32_t base = 0;
+      for (; base + 64u * GS_COOP_PAIRS < coop_total; base += 64u * GS_COOP_PAIRS) {
+        coop_bump(base);
+        coop_collect();
+      }
+      coop_bump(base);
+    }
+    // what is final before the colour is stored ahead of it: the registers serve the SH row
+    if (idx < a.P) store_geometry();
+    if (reached) finish();
+    if (idx < a.P) {
+      if (write_record) store_record(1);
+      collect();
+    }
+  } else if (idx < a.P) {
+    store_geometry();
+    if (write_record) store_record(1);
     collect();  // (the last batch of bucket slots: nothing pending outside region mode)
     // key of the per-Gaussian depth sort (gs_binning.hip): culled Gaussians sort behind everything
     if (a.tile_cull != 2) g.depth_keys[idx] = tiles ? __float_as_uint(sp.depth) : 0xFFFFFFFFu;
-    a.radii[idx] = radius_out;
   }
+  if constexpr (COOP) coop_collect();  // (every lane: the pairs it took are other lanes' Gaussians)
   // per-workgroup partial sum of tiles_touched for the prefix sum
   __shared__ uint32_t red[GS_BLOCK / 64];
   uint32_t v = tiles;
@@ -471,10 +614,32 @@ __global__ void __launch_bounds__(GS_BLOCK) mark_visible_kernel(int P, const flo
   present[idx] = !(pv.z <= 0.2f);
 }
 
+// Region mode: 1 = the cooperative form of preprocess_fwd_kernel (a wave shares the regions of its large footprints), 0 = the
+// per-lane form.  GS_REGION_COOP, read once; gs_region_coop sets it for the launches that follow (both forms give the same
+// lists bit for bit: the control arm of a measurement).
+static int g_region_coop = -1;
+static int region_coop_form() {
+  if (g_region_coop < 0) {
+    const char* e = getenv("GS_REGION_COOP");
+    g_region_coop = e ? (atoi(e) != 0 ? 1 : 0) : GS_REGION_COOP_DEFAULT;
+  }
+  return g_region_coop;
+}
+extern "C" int gs_region_coop(int32_t form) {
+  if (form >= 0) g_region_coop = form ? 1 : 0;
+  return region_coop_form();
+}
+
 int launch_preprocess_fwd(const PreprocessArgs& a, const GeomView& g, hipStream_t s) {
   const int nb = (a.P + GS_BLOCK - 1) / GS_BLOCK;
   const size_t lds = preprocess_limit_lds_floats(a);
-  hipLaunchKernelGGL(preprocess_fwd_kernel, dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
+  // (the cooperative form packs a region into 26 bits and a region row or column into 16)
+  const bool coop = a.tile_cull == 2 && region_coop_form() && a.rg_x <= 0xFFFF && a.rg_y <= 0xFFFF &&
+                    (long long)a.rg_x * a.rg_y <= (1ll << 26);
+  if (coop)
+    hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
+  else
+    hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
   return 0;
 }
 int launch_scan_block_sums(const GeomView& g, int P, hipStream_t s) {

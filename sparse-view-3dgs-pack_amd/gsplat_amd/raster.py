@@ -451,6 +451,18 @@ class RasterBackend:
     # the stream hand-offs cost more than the hidden stream saves); GS_TWO_PHASE_STEP=0 switches it off.
     # depth-limited lists for callers that name their cameras (GaussianRasterizer.camera_key); GS_KEYED_LIMITS=0: never
     force_rowwise_entries = False
+
+    # region binning: which form of the forward geometry kernel fills the buckets (gs_region_coop: True = a wave shares the
+    # regions of its large footprints, False = every lane walks its own; same lists bit for bit).  Process-wide, like the
+    # library's GS_REGION_COOP it overrides; only the device library has it.
+    @property
+    def region_coop(self):
+        return bool(self.api.raw("region_coop")(-1))
+
+    @region_coop.setter
+    def region_coop(self, on):
+        self.api.raw("region_coop")(int(bool(on)))
+
     # test hook: called as scratch_fill(kind, tensor) right after each fresh scratch buffer of rasterize_gaussians is allocated
     # (kind "geom", "img", "binning"), so that a test decides what the buffer holds before the forward runs instead of the
     # caching allocator (tests/test_gpu_scratch_reuse.py); None: nothing happens
