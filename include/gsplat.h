@@ -569,6 +569,38 @@ int gs_pearson_fwd(const float* x, const float* t, int64_t n, int32_t form_a, in
 int gs_pearson_bwd(const float* x, const float* t, int64_t n, int32_t form_a, int32_t form_b, int32_t flags, const void* tmp,
                    const float* dout_dev, float* grad_x /*[n]*/, float* grad_t /*[n]*/, void* stream);
 
+/* ---- DNGaussian's neural colour and opacity heads (scene/neural_renderer.py, GridRenderer; csrc/gs_mlp.hip) ----
+ * Two bias-free ReLU MLPs on per-Gaussian encodings, each direction ONE fused launch on the f32 MFMA:
+ *   sigma_net  enc_x [B,32] -> 64 -> 64 -> 65: column 0 = sigma [B], columns 1..64 = geo_feat
+ *   color_net  [enc_d [B,16] | geo_feat] -> 64 -> 3, color [B,3] = sigmoid(.) * 1.002 - 0.001
+ * Weights in torch.nn.Linear layout [out,in], contiguous fp32: w_s0 [64,32], w_s1 [64,64], w_s2 [65,64], w_c0 [64,80],
+ * w_c1 [3,64].  No activation ever reaches device memory.
+ * Forward: enc_d = color = NULL is the sigma-only form (w_c0 / w_c1 are then not read); otherwise both are required.
+ * Backward: recomputes the forward.  g_sigma [B] and g_color [B,3] are each nullable (= zero); g_enc_x [B,32], g_enc_d [B,16]
+ * and the weight gradients are nullable outputs and a NULL output is not computed; the weight gradients are requested all
+ * together (three in the sigma-only form enc_d = NULL, else five).  They need tmp: >= gs_dng_heads_tmp_bytes(B) bytes of
+ * device scratch, one partial per workgroup, added in workgroup order by a second small launch: no atomics, the same bits on
+ * every run.  ReLU'(0) = 0.  A workgroup takes GS_DNG_HEADS_TILE_ROWS rows at a time; the backward's grid is at most
+ * GS_DNG_HEADS_MAX_BLOCKS workgroups, which stride over what is left (the forward: as many for the colour form, twice as many
+ * for the sigma-only form).  max_blocks > 0 caps either grid further (0: no cap; tests use it to make every workgroup take
+ * several tiles of a small batch); it changes the order in which the weight gradients are summed, nothing else.
+ * GS_E_NULL: a required pointer is missing; GS_E_SHAPE: B < 0, max_blocks < 0, or tmp_bytes smaller than B needs.  B = 0: returns 0, the forward
+ * launches nothing, the backward zeroes the weight gradients.  Everything is enqueued on `stream`; no host synchronisation. */
+#define GS_DNG_ENC_X 32
+#define GS_DNG_ENC_D 16
+#define GS_DNG_HIDDEN 64
+#define GS_DNG_GEO 64
+#define GS_DNG_HEADS_TILE_ROWS 128
+#define GS_DNG_HEADS_MAX_BLOCKS 256
+size_t gs_dng_heads_tmp_bytes(int64_t B);
+int gs_dng_heads_fwd(const float* enc_x, const float* enc_d, int64_t B, const float* w_s0, const float* w_s1, const float* w_s2,
+                     const float* w_c0, const float* w_c1, float* sigma /*[B]*/, float* color /*[B,3]*/, int32_t max_blocks,
+                     void* stream);
+int gs_dng_heads_bwd(const float* enc_x, const float* enc_d, int64_t B, const float* w_s0, const float* w_s1, const float* w_s2,
+                     const float* w_c0, const float* w_c1, const float* g_sigma, const float* g_color, float* g_enc_x,
+                     float* g_enc_d, float* g_w_s0, float* g_w_s1, float* g_w_s2, float* g_w_c0, float* g_w_c1, void* tmp,
+                     size_t tmp_bytes, int32_t max_blocks, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

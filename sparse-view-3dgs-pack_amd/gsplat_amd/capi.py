@@ -174,6 +174,9 @@ PROTOTYPES = {
     "pearson_tmp_bytes": (_SZ, [_I64]),
     "pearson_fwd": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P, _P]),
     "pearson_bwd": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "dng_heads_tmp_bytes": (_SZ, [_I64]),
+    "dng_heads_fwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "dng_heads_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I32, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -243,7 +246,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                "depth_norm_tmp_bytes", "depth_norm_fwd", "depth_norm_bwd", "depth_smooth_fwd", "depth_smooth_bwd",
                "dng_depth_reg_fwd", "dng_depth_reg_bwd",
                # FSGS's Pearson depth loss: restated in torch (tests/fsgs_loss_reference.py)
-               "pearson_tmp_bytes", "pearson_fwd", "pearson_bwd")
+               "pearson_tmp_bytes", "pearson_fwd", "pearson_bwd",
+               # DNGaussian's neural heads: restated in torch (tests/neural_reference.py)
+               "dng_heads_tmp_bytes", "dng_heads_fwd", "dng_heads_bwd")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 
