@@ -601,6 +601,39 @@ int gs_dng_heads_bwd(const float* enc_x, const float* enc_d, int64_t B, const fl
                      float* g_enc_d, float* g_w_s0, float* g_w_s1, float* g_w_s2, float* g_w_c0, float* g_w_c1, void* tmp,
                      size_t tmp_bytes, int32_t max_blocks, void* stream);
 
+/* ---- DNGaussian's per-Gaussian regulariser, view directions and near-camera mask (csrc/gs_dng_reg.hip) ----
+ * Regulariser over scaling [P,3] (positive) and opacity [P] (in (0,1)), P >= 1, fp32:
+ *   mx_i / mn_i = row max / min of scaling (a tie goes to the lowest column), H = {o_i > 0.2f}, L = {o_i < 0.2f}
+ *   shape = mean mx_i / mn_i, scale = mean mx_i^2, opa = 1 - mean_H o_i^2 + mean_L (1 - o_i)^2,
+ *   total = w_shape shape + w_scale scale + w_opa opa;      out[4] = shape, scale, opa, total
+ * Each ratio and square is taken in fp32, the sums are float64 in one fixed order (the same bits on every run).  o_i == 0.2f is
+ * in neither set; an empty set makes opa and total NaN while every gradient element stays finite.
+ * GS_DNG_REG_RAW: scaling and opacity are the model's raw rows, s = exp(.), o = sigmoid(.) are evaluated in the kernel and the
+ * gradients are with respect to the raw values; no activated tensor is written.
+ * Forward: two launches; a workgroup sweeps GS_DNG_REG_BLOCK_ROWS rows at a time, the grid is at most GS_DNG_REG_MAX_BLOCKS
+ * workgroups (max_blocks > 0 caps it further, 0: no cap; tests use it to make a small P stride) and strides over what is left.
+ * tmp: >= gs_dng_reg_tmp_bytes(P) bytes of device scratch (0: P out of range); the forward leaves in it what the backward of the
+ * SAME arguments reads.  Backward: one launch.  g_terms [3] = dL/d(shape, scale, opa) and g_total [1] = dL/dtotal are read
+ * from device memory, each nullable (= zero), not both; g_scaling [P,3] (every column written, nothing to zero beforehand) and
+ * g_opacity [P] are each nullable (that half is skipped), not both.
+ * gs_view_dirs_*: out_i = (x_i - c) / |x_i - c| for xyz [P,3] and campos [3] (device memory); the backward gives
+ * g_xyz_i = (g_i - n_i (n_i . g_i)) / |x_i - c|, nothing to campos.  A row at the camera centre is NaN.
+ * gs_near_mask: mask_i (one byte, 0 / 1) = OR_k (|x_i - c_k| < near) for centers [K,3] (device memory), K >= 1, norm in fp32.
+ * One launch each.  GS_E_NULL: a required pointer is missing; GS_E_SHAPE: P < 1, K < 1, P out of range, max_blocks < 0 or an
+ * unknown flag.  Everything is enqueued on `stream`; no host synchronisation, no atomics. */
+#define GS_DNG_REG_RAW 1
+#define GS_DNG_REG_BLOCK_ROWS 1024
+#define GS_DNG_REG_MAX_BLOCKS 1024
+size_t gs_dng_reg_tmp_bytes(int64_t P);
+int gs_dng_reg_fwd(const float* scaling, const float* opacity, int64_t P, double w_shape, double w_scale, double w_opa,
+                   int32_t flags, int32_t max_blocks, void* tmp, float* out /*[4]*/, void* stream);
+int gs_dng_reg_bwd(const float* scaling, const float* opacity, int64_t P, int32_t flags, const void* tmp, const float* g_terms,
+                   const float* g_total, float* g_scaling /*[P,3]*/, float* g_opacity /*[P]*/, void* stream);
+int gs_view_dirs_fwd(const float* xyz, const float* campos, int64_t P, float* out /*[P,3]*/, void* stream);
+int gs_view_dirs_bwd(const float* xyz, const float* campos, int64_t P, const float* g /*[P,3]*/, float* g_xyz /*[P,3]*/,
+                     void* stream);
+int gs_near_mask(const float* xyz, int64_t P, const float* centers, int32_t K, float near, uint8_t* mask /*[P]*/, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

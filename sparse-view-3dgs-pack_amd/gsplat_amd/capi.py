@@ -177,6 +177,12 @@ PROTOTYPES = {
     "dng_heads_tmp_bytes": (_SZ, [_I64]),
     "dng_heads_fwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _I32, _P]),
     "dng_heads_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I32, _P]),
+    "dng_reg_tmp_bytes": (_SZ, [_I64]),
+    "dng_reg_fwd": (C.c_int, [_P, _P, _I64, C.c_double, C.c_double, C.c_double, _I32, _I32, _P, _P, _P]),
+    "dng_reg_bwd": (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _P, _P]),
+    "view_dirs_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "view_dirs_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "near_mask": (C.c_int, [_P, _I64, _P, _I32, _F, _P, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -248,7 +254,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # FSGS's Pearson depth loss: restated in torch (tests/fsgs_loss_reference.py)
                "pearson_tmp_bytes", "pearson_fwd", "pearson_bwd",
                # DNGaussian's neural heads: restated in torch (tests/neural_reference.py)
-               "dng_heads_tmp_bytes", "dng_heads_fwd", "dng_heads_bwd")
+               "dng_heads_tmp_bytes", "dng_heads_fwd", "dng_heads_bwd",
+               # DNGaussian's per-Gaussian regulariser, view directions, near mask: restated in torch (tests/dng_reg_reference.py)
+               "dng_reg_tmp_bytes", "dng_reg_fwd", "dng_reg_bwd", "view_dirs_fwd", "view_dirs_bwd", "near_mask")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 
