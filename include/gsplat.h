@@ -380,6 +380,17 @@ typedef struct GsStepState {
    * parameter moves by the old momentum).  Visible Gaussians without instances (culled spans, depth limits) still take
    * their zero-gradient step.  Blocks of 256 rows without a visible Gaussian cost no parameter or moment traffic. */
   int32_t sparse;
+  /* 1: "a Gaussian with instances" means, for this step's tail, one that owns a list entry the BACKWARD BLEND VISITS (in front of
+   * its tile's deepest last contributor; the forward blend leaves one byte per Gaussian saying so in the geometry buffer) instead
+   * of one that emitted instances at all.  The others - accepted by a tile but lying behind every pixel's saturation, a quarter
+   * to a third of the accepted ones on a trained scene - have all-zero sums, hence exact-zero gradients: gs_step_uninstanced
+   * steps them beside the blend, the chain and the per-Gaussian kernel of gs_backward_step never read their rows.  Same
+   * parameters, moments and statistics as with 0 (a moment may differ in the sign of a zero).  Give the SAME value to
+   * gs_step_uninstanced and to gs_backward_step.  Ignored - the split stays on tiles_touched - with rows_override, in the
+   * data-parallel form, and when the forward blend did not write the flags (GS_REACHED_SPLIT=0 in the environment).
+   * (The field lies in what was padding behind `sparse`: no offset and no size changed, a caller that zero-fills the struct
+   * gets the old behaviour.) */
+  int32_t reached_split;
   /* Gradients-out form with the split SH layout (GsGaussians.shs_rest != NULL): grad_out[1] receives the gradient of
    * _features_dc [P,1,3] and grad_out_rest that of _features_rest [P,M-1,3] - each a contiguous tensor as autograd's
    * AccumulateGrad wants it (a strided slice of one [P,16,3] buffer is copied again).  NULL with the one-row layout. */
@@ -406,7 +417,8 @@ int gs_backward_step_x(const GsView* view, const GsGaussians* g, const int32_t* 
  * bound by vector issue and leaves HBM idle (next to the criterion's kernels it gains nothing: they slow down by what it
  * takes, measured).  gs_backward_step steps the Gaussians with instances; its per-Gaussian kernel must be ordered after
  * this call (st->phase1_done; the two split the float4s of the parameter rows between them).  Like gs_backward_step a no-op on the device when the forward had flagged
- * overflow or trunc_failed - so it must not start before the forward BLEND has finished.  Same element arithmetic: the
+ * overflow or trunc_failed, and with st->reached_split it reads the per-Gaussian flags the forward blend writes - so it must
+ * not start before the forward BLEND has finished.  Same element arithmetic: the
  * two calls together leave the bits gs_backward_step (phase 0) leaves.  With tile_cull = 0 every visible Gaussian has
  * instances, and the Gaussians without are the ones outside the frustum (59 % of bench.py's scene: with the rows in spatial
  * order most of their blocks are dormant, see GsStepState.dormant).  GS_E_UNSUPPORTED in the data-parallel form.

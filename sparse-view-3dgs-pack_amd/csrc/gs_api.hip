@@ -25,6 +25,17 @@ static int check_args(const GsView* v, const GsGaussians* g) {
   return GS_OK;
 }
 
+// GS_REACHED_SPLIT (read once; default on): 0 = the forward blend does not fill GeomView.reached, and the fused step's tail
+// then splits the Gaussians on tiles_touched whatever GsStepState.reached_split says (the header's HDR_REACHED word stays 0)
+static bool reached_marking() {
+  static const bool on = [] { const char* e = getenv("GS_REACHED_SPLIT"); return !(e && atoi(e) == 0); }();
+  return on;
+}
+// does the tail of this fused step split on the reached flags?  (Not with given rows: they are not this forward's sums.)
+static inline bool step_uses_reached(const GsStepState* st) {
+  return st && st->reached_split && !st->rows_override && !st->grad_out[0];
+}
+
 static inline void tile_grid(const GsView* v, int& gx, int& gy) {
   gx = (v->image_width + TILE_X - 1) / TILE_X;
   gy = (v->image_height + TILE_Y - 1) / TILE_Y;
@@ -291,7 +302,8 @@ static int forward_render_impl(const GsView* v, const GsGaussians* g, GsScratch*
     GS_PROF(ST_RENDER_FWD, s);
     launch_render_fwd_wave(iv.ranges, bv.vals[0], W, H, gx, gy, gv.splat, v->bg, iv.final_T, iv.n_contrib, iv.tile_work,
                            sc->tile_order_hint, sc->tile_depth_limit, iv.tile_stop_depth, &gv.hdr->trunc_failed, out_color,
-                           out_invdepth, out_extra, fsgs, v->tile_cull ? 0 : 1, s);
+                           out_invdepth, out_extra, fsgs, v->tile_cull ? 0 : 1, s, reached_marking() ? gv.reached : nullptr,
+                           &gv.hdr->pad[HDR_REACHED]);
   }
   if (!sc->defer_tile_order) {
     GS_PROF(ST_TILE_ORDER, s);
@@ -347,6 +359,8 @@ static PreprocessBwdArgs preprocess_bwd_args(const GsView* v, const GsGaussians*
   a.raw_activations = g->raw_activations;
   a.skip_uninstanced = 0;
   a.tiles_touched = gv.tiles_touched;
+  a.reached = nullptr;
+  a.reached_flag = nullptr;
   a.colors_precomp = g->colors_precomp;
   a.scale_modifier = v->scale_modifier;
   a.cov3D = g->cov3D_precomp ? g->cov3D_precomp : gv.cov3D;
@@ -467,6 +481,10 @@ static int backward_impl(const GsView* v, const GsGaussians* g, const int32_t* r
   //  is the same thing there; the two-phase step splits the Gaussians on it in either list mode)
   a.skip_uninstanced = (v->tile_cull || (step && step->phase == 2)) ? 1 : 0;
   a.clean_rows = rows_clean != 0;
+  if (step_uses_reached(step)) {
+    a.reached = gv.reached;
+    a.reached_flag = &gv.hdr->pad[HDR_REACHED];
+  }
   if (step && step->extra) {  // per-wave partial sums of dL/dgain: behind the records
     float* gp = reinterpret_cast<float*>((char*)workspace + gs_align((size_t)P * GR_ROW_BYTES) + gs_align((size_t)P * GC_REC_BYTES));
     a.extra_raw = step->extra;
@@ -538,6 +556,10 @@ int gs_step_uninstanced(const GsView* v, const GsGaussians* g, const int32_t* ra
   const GsGrads none = {};
   PreprocessBwdArgs a = preprocess_bwd_args(v, g, radii, gv, 0, nullptr, nullptr, &none);
   a.skip_uninstanced = 1;
+  if (step_uses_reached(st)) {  // (the very rule of gs_backward_step: the two calls split the Gaussians between them)
+    a.reached = gv.reached;
+    a.reached_flag = &gv.hdr->pad[HDR_REACHED];
+  }
   sa.hdr = gv.hdr;
   sa.phase = 1;
   {

@@ -8,6 +8,7 @@
 //           tiles_touched[P] u32
 //           block_sums / sorted_sums [ceil(P/256)+1] u32   workgroup sums of tiles_touched (index / depth order)
 //           gsort            radix-sort buffers of the per-Gaussian depth sort (16 B x P + histograms)
+//           reached[P] u8    1 = the forward blend walked over a list entry of this Gaussian that the backward blend will visit
 //  img    : final_T[N] f32 | n_contrib[N] u32 | ranges[T] uint2 | tile_work[T] u32 | tile_order[T] u32 | region_count[<= T] u32
 //  binning: keys[2][cap] u32 | Gaussian ids[2][cap] u32 | radix histograms   (16 B per instance of capacity) | region / chunk /
 //           tile tables (gs_tilebin.hip).  tile_cull = 0 / 1: the arrays hold the region ENTRIES (key = region id | tile mask << 16)
@@ -41,9 +42,12 @@ struct GeomHeader {
                           // pad[HDR_SIDE_CURSOR]: next Gaussian block of step_uninstanced_kernel (zeroed with the header)
                           // pad[HDR_LIMITED]: 1 if the geometry phase ran with depth limits - then a Gaussian with
                           // tiles_touched == 0 may have no record of this forward (gs_preprocess.hip), 0 otherwise
+                          // pad[HDR_REACHED]: 1 once the forward blend of this geometry state has filled GeomView.reached
+                          // (zeroed by the geometry phase), 0: no blend has, the flags say nothing
 };
 #define HDR_SIDE_CURSOR 1
 #define HDR_LIMITED 2
+#define HDR_REACHED 3
 static_assert(sizeof(GeomHeader) == 256, "header is one 256-B block");
 
 // 64-byte per-Gaussian record written by the forward preprocess kernel.
@@ -111,11 +115,13 @@ struct GeomView {
   uint32_t* sorted_sums;  // [nb+1] the same in depth order (instance emission)
   uint32_t* depth_keys;   // [P] depth bits (0xFFFFFFFF when culled): read-only input of the depth sort
   SortBufs gsort;         // ping-pong buffers of the depth sort of the P Gaussians
+  uint8_t* reached;       // [P] zeroed by the geometry phase; the forward blend stores 1 for every Gaussian that owns a list
+                          // entry in front of its tile's tile_work - the only ones whose gradient rows can be non-zero
 };
 static inline __host__ __device__ size_t geom_bytes(size_t P) {
   size_t nb = (P + GS_BLOCK - 1) / GS_BLOCK;
   return sizeof(GeomHeader) + gs_align(64 * P) + gs_align(24 * P) + 2 * gs_align(4 * P) + 2 * gs_align(4 * (nb + 1)) +
-         sort_bytes(P);
+         sort_bytes(P) + gs_align(P);
 }
 static inline __host__ __device__ GeomView geom_view(void* buf, size_t P) {
   char* p = (char*)buf;
@@ -128,7 +134,8 @@ static inline __host__ __device__ GeomView geom_view(void* buf, size_t P) {
   g.block_sums = (uint32_t*)p; p += gs_align(4 * (nb + 1));
   g.sorted_sums = (uint32_t*)p; p += gs_align(4 * (nb + 1));
   g.depth_keys = (uint32_t*)p; p += gs_align(4 * P);
-  g.gsort = sort_view(p, P);
+  g.gsort = sort_view(p, P); p += sort_bytes(P);
+  g.reached = (uint8_t*)p;
   return g;
 }
 
@@ -320,7 +327,8 @@ int launch_export_keys_region(const uint2* ranges, const uint32_t* point_list, c
 int launch_render_fwd_wave(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y,
                            const Splat* splat, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_work,
                            const uint32_t* order_hint, const float* depth_limit, float* stop_depth, uint32_t* trunc_failed,
-                           float* out_color, float* out_invdepth, float* out_extra, int fsgs, int cull, hipStream_t s);
+                           float* out_color, float* out_invdepth, float* out_extra, int fsgs, int cull, hipStream_t s,
+                           uint8_t* reached = nullptr, uint32_t* reached_flag = nullptr);
 // tile_order[] = per XCD band of the image, the tiles by decreasing tile_work[] (order inside a bucket of equal work is free)
 int launch_export_stop_depth(const float* stop_depth, float* out, int grid_x, int grid_y, hipStream_t s);
 int launch_tile_order(const uint32_t* tile_work, uint32_t* tile_order, int T, uint32_t* order_out, const float* stop_depth,
@@ -368,11 +376,23 @@ struct PreprocessBwdArgs {
   float* grad_recs;           // [P][GC_STRIDE]: written by the chain kernel, read by the streaming kernels
   int clean_rows;          // gs_backward_step (GsStepState.rows_clean): the chain kernel zeroes every row it has consumed
   const uint32_t* tiles_touched;  // [P] instances each Gaussian emitted in this forward (skip_uninstanced)
+  const uint8_t* reached;         // NULL, or GeomView.reached (the fused step with GsStepState.reached_split): the chain and step
+                                  // kernels then split the Gaussians on `reached != 0` instead of `tiles_touched != 0` - provided the
+                                  // forward blend filled the flags (reached_flag, the header's HDR_REACHED word); see gs_instanced
+  const uint32_t* reached_flag;
   const Splat* splat;
   GsGrads out;
 };
 // the float64 covariance chain of every Gaussian with sums: rows -> records (hdr != NULL: a forward that flagged overflow /
 // trunc_failed leaves nothing to compute - only the rows are cleaned)
+// "instanced" for the backward's tail: does Gaussian idx take part in this view's gradients?  With the reached flags: only if
+// the backward blend can have added to its row (every other row is all-zero, so its gradients are exact zeros).
+static inline __device__ bool gs_use_reached(const PreprocessBwdArgs& a) {
+  return a.reached != nullptr && a.reached_flag[0] != 0u;
+}
+static inline __device__ bool gs_instanced(const PreprocessBwdArgs& a, bool use_reached, int idx) {
+  return use_reached ? a.reached[idx] != 0 : a.tiles_touched[idx] != 0u;
+}
 int launch_chain(const PreprocessBwdArgs& a, const GeomHeader* hdr, hipStream_t s);
 int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s);
 // the same stage with the train step's tail fused in (gs_backward_step); bias corrections precomputed on the host

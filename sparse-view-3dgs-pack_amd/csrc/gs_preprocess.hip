@@ -151,7 +151,10 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
   asm volatile("" : "+v"(op_in), "+v"(sc_in.x), "+v"(sc_in.y), "+v"(sc_in.z), "+v"(rq_in.x), "+v"(rq_in.y), "+v"(rq_in.z),
                "+v"(rq_in.w));
   const GsLdsFloatPtr lds_seg = (GsLdsFloatPtr)s_limit + (GS_LIMIT_TILES_IN_LDS ? T : 0);
-  if (idx == 0) g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
+  if (idx == 0) {
+    g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
+    g.hdr->pad[HDR_REACHED] = 0u;  // (set again by the forward blend that fills g.reached)
+  }
   // region mode: the bound of region (rx, ry) = the largest of its (up to) four row-segment bounds: a pair within its TILE's
   // bound lies in a region it is not beyond
   const int segs_x = (int)depth_limit_segs_x((uint32_t)a.grid_x);
@@ -261,6 +264,7 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
       cd[2] = make_float2(cov3D[4], cov3D[5]);
     }
     g.tiles_touched[idx] = tiles;
+    g.reached[idx] = 0;  // (every forward starts clean: the blend stores the ones, gs_render_fwd_wave.hip)
     a.radii[idx] = radius_out;
   };
 

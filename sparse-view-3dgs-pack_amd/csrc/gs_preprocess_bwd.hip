@@ -18,7 +18,9 @@
 // chain_kernel: rows (float64 blend sums) -> records (fp32 results of the float64 covariance chain), one thread per
 // Gaussian, only those with sums do anything.  Registers are not an issue here (2 waves per SIMD allowed: the chain's
 // ~170 VGPRs), the launch is ~10 us at 1 M Gaussians.  With clean_rows it zeroes each row it has read, so the rows are
-// all-zero again for the next view's blend backward and no clear launch is needed (GsStepState.rows_clean).
+// all-zero again for the next view's blend backward and no clear launch is needed (GsStepState.rows_clean).  With the reached
+// flags (PreprocessBwdArgs.reached) "with sums" means "named by a list entry the backward blend visited": the row of any other
+// Gaussian received no atomic, so it is still all-zero - clean without having been read - and its gradients are exact zeros.
 // ------------------------------------------------------------------------------------------------------------------
 // Only a fifth of the Gaussians have sums on depth-limited lists, scattered over the index range: one thread per Gaussian
 // would run the ~700 double-precision instructions of the chain in EVERY wave at 20 % lane occupancy (measured: 33 us).  So
@@ -31,10 +33,15 @@ __global__ void __launch_bounds__(64, 3) chain_kernel(PreprocessBwdArgs a, const
   const int lane = threadIdx.x;
   const int base = blockIdx.x * CHAIN_PER_WAVE;
   bool has[CHAIN_PER_WAVE / 64];
+  const bool use_reached = gs_use_reached(a);
+  // The multispectral step adds one term per list entry to the wave's dL/dgain, lane by lane: which lane holds which Gaussian
+  // decides the rounding of that sum.  So with gain_partials the list stays the one of tiles_touched (every term keeps its
+  // lane, the sum its bits) and an unreached Gaussian - its term is an exact zero - is merely skipped where its lane meets it.
+  const bool list_reached = use_reached && !a.gain_partials;
 #pragma unroll
   for (int k = 0; k < CHAIN_PER_WAVE / 64; k++) {   // (all flag loads in flight before the first is used)
     const int idx = base + k * 64 + lane;
-    has[k] = idx < a.P && a.radii[idx] > 0 && !(a.skip_uninstanced && a.tiles_touched[idx] == 0);
+    has[k] = idx < a.P && a.radii[idx] > 0 && !(a.skip_uninstanced && !gs_instanced(a, list_reached, idx));
   }
   int n = 0;
 #pragma unroll
@@ -58,6 +65,7 @@ __global__ void __launch_bounds__(64, 3) chain_kernel(PreprocessBwdArgs a, const
   }
   for (int j = lane; j < n; j += 64) {
     const int idx = s_list[j];
+    if (use_reached && !list_reached && a.reached[idx] == 0) continue;  // (no atomic landed in its row: clean, nothing to chain)
     gs_row_t* row = const_cast<gs_row_t*>(a.grad_rows) + (size_t)idx * GR_STRIDE;
     float* rec = a.grad_recs + (size_t)idx * GC_STRIDE;
     if (!failed) {
@@ -389,7 +397,8 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_step_kernel(Prepro
   const float b1 = st.beta1, b2 = st.beta2, eps = st.eps;
   // a Gaussian that emitted no instance (culled spans, depth limits) has all-zero blend sums, hence zero gradients: it
   // still counts as seen (statistics) and still takes its Adam step, but its records, sums and SH row are not read
-  const bool instanced = !(a.skip_uninstanced && a.tiles_touched[idx] == 0);
+  // (with the reached flags: one the backward blend never visited - the same exact zeros, see chain_kernel)
+  const bool instanced = !(a.skip_uninstanced && !gs_instanced(a, gs_use_reached(a), idx));
   const bool mine = PHASE == 0 || (in_range && instanced);  // this launch does this Gaussian's statistics
   // adam_block's flags: bit 0 = a Gaussian WITHOUT instances (the other phase's), bit 1 = not stepped at all (sparse_adam: not visible)
   if (s_sel) s_sel[tid] = (unsigned char)(((PHASE != 0 && in_range && !instanced) ? 1 : 0) | ((sparse && !visible) ? 2 : 0));
@@ -579,6 +588,7 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) step_uninstanced_kernel(Preproces
   }
   const float b1 = st.beta1, b2 = st.beta2, eps = st.eps;
   const bool sparse = st.sparse != 0;
+  const bool use_reached = gs_use_reached(a);  // (the split of phase 2: this launch steps whatever that one does not)
   const int tid = threadIdx.x;
   struct Zero {
     __device__ __forceinline__ float operator()(int) const { return 0.f; }
@@ -599,7 +609,7 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) step_uninstanced_kernel(Preproces
     }
     const int idx = blk * GS_BLOCK + tid;
     const bool in_range = idx < a.P;
-    const bool mine = in_range && a.tiles_touched[idx] == 0;
+    const bool mine = in_range && !gs_instanced(a, use_reached, idx);
     const int radius = (mine && (st.max_radii2D || sparse)) ? a.radii[idx] : 0;
     const bool frozen = sparse && radius <= 0;   // sparse_adam: a Gaussian that is not visible in this view is not stepped
     s_sel[tid] = (unsigned char)((mine ? 1 : 0) | (frozen ? 2 : 0));

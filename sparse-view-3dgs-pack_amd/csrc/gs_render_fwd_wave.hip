@@ -32,7 +32,9 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
                                                              uint32_t* __restrict__ trunc_failed,
                                                              float* __restrict__ out_color,
                                                              float* __restrict__ out_invdepth,
-                                                             float* __restrict__ out_extra) {
+                                                             float* __restrict__ out_extra,
+                                                             uint8_t* __restrict__ reached,
+                                                             uint32_t* __restrict__ reached_flag) {
   __shared__ float4 s_a[WB];  // x, y, invdepth, cull extent y (CULL) / view depth (!CULL)
   __shared__ float4 s_c[WB];  // conic, opacity
   __shared__ float4 s_k[WB];  // rgb, cull extent x
@@ -179,6 +181,16 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) lmax = max(lmax, (uint32_t)__shfl_xor((int)lmax, off, 64));
     if (lane == 0) tile_work[tile] = lmax;
+    // GeomView.reached (optional; the fused step's tail splits the Gaussians on it): the backward blend of this tile visits
+    // exactly the list positions < lmax, so the Gaussians named there - over all tiles - are the only ones whose gradient rows
+    // can become non-zero.  Marked here, from the wave-uniform lmax, rather than batch by batch inside the loop: nothing lives
+    // across the loop for it, and entries the forward only walked over on its way to the saturating one (behind the deepest
+    // last contributor) stay unmarked.  The ids are re-read from point_list (coalesced, in L2); several tiles store the
+    // same 1 to a byte: plain stores, no atomics, no read-modify-write.
+    if (reached) {
+      for (uint32_t p = (uint32_t)lane; p < lmax; p += WB) reached[point_list[range.x + p]] = 1;
+      if (tile == 0 && lane == 0) *reached_flag = 1u;
+    }
   }
   const size_t HW = (size_t)H * W;
   const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
@@ -203,11 +215,12 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
 int launch_render_fwd_wave(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y,
                            const Splat* splat, const float* bg, float* final_T, uint32_t* n_contrib, uint32_t* tile_work,
                            const uint32_t* order_hint, const float* depth_limit, float* stop_depth, uint32_t* trunc_failed,
-                           float* out_color, float* out_invdepth, float* out_extra, int fsgs, int cull, hipStream_t s) {
+                           float* out_color, float* out_invdepth, float* out_extra, int fsgs, int cull, hipStream_t s,
+                           uint8_t* reached, uint32_t* reached_flag) {
 #define GS_FWD_WAVE(EX, FS, CU)                                                                                          \
   hipLaunchKernelGGL((render_fwd_wave_kernel<EX, FS, CU>), dim3(((grid_x * grid_y + 7) / 8) * 8), dim3(64), 0, s, ranges, point_list, W, H, \
                      grid_x, splat, bg, final_T, n_contrib, tile_work, order_hint, cull ? nullptr : depth_limit, stop_depth, trunc_failed, out_color,   \
-                     out_invdepth, out_extra)
+                     out_invdepth, out_extra, reached, reached_flag)
   if (fsgs) {
     if (cull) GS_FWD_WAVE(false, true, true); else GS_FWD_WAVE(false, true, false);
   } else if (out_extra) {

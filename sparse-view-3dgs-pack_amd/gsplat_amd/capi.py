@@ -108,6 +108,7 @@ class GsStepState(C.Structure):
                 ("gain_m", C.c_void_p), ("gain_v", C.c_void_p), ("lr_extra", C.c_float), ("lr_gain", C.c_float),
                 ("step_extra", C.c_int32), ("step_gain", C.c_int32), ("grad_out_extra", C.c_void_p),
                 ("grad_out_gain", C.c_void_p), ("grad_mask", C.c_void_p), ("dormant", C.c_void_p), ("sparse", C.c_int32),
+                ("reached_split", C.c_int32),   # (in what was padding behind `sparse`: same size, same offsets)
                 ("grad_out_rest", C.c_void_p)]
 
 

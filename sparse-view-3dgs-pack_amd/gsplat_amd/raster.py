@@ -483,6 +483,11 @@ class RasterBackend:
         return side
     TWO_PHASE = os.environ.get("GS_TWO_PHASE_STEP", "1") != "0"
     TWO_PHASE_MIN_P = 100_000
+    # GsStepState.reached_split: the fused step's tail counts a Gaussian as instanced only when the backward blend visits one of
+    # its list entries (the forward blend leaves the flags); the others - accepted by a tile, but behind every pixel's
+    # saturation - take their zero-gradient step on the side stream.  GS_REACHED_SPLIT=0 (which also stops the library's
+    # forward from writing the flags) or False: the split stays on tiles_touched.
+    REACHED_SPLIT = os.environ.get("GS_REACHED_SPLIT", "1") != "0"
 
     def _two_phase(self, step, P):
         """Does the fused backward of `step` over P Gaussians run in two phases?  (Not its gradients-out form; with
@@ -521,7 +526,8 @@ class RasterBackend:
         # (a CU-masked side stream - hipExtStreamCreateWithCUMask, 64 / 96 / 128 CUs - was tried in round 4: the two
         #  queues then did not overlap at all, every kernel of the step ran ~10 % slower, step 0.98 -> 1.18-1.20 ms)
         side = self._side_stream(device)
-        side.wait_stream(main)   # (the forward has decided overflow / trunc_failed)
+        side.wait_stream(main)   # (the forward blend has decided overflow / trunc_failed and left the reached flags)
+        step.reached_split = int(self.REACHED_SPLIT)   # (the backward takes the same struct: phase 2 splits the same way)
         self.api.call("step_uninstanced", C.byref(view), C.byref(g), radii.contiguous().data_ptr(), C.byref(s),
                       C.byref(step), C.c_void_p(side.cuda_stream))
         done = torch.cuda.Event()
@@ -918,6 +924,8 @@ class RasterBackend:
             if last is f and last.step is step:
                 done = last.done          # (issued by launch_uninstanced_early, under the criterion's backward)
             last.step = last.radii = last.img = last.done = None
+        if done is None:
+            step.reached_split = int(self.REACHED_SPLIT)
         if self._two_phase(step, P):
             if done is None:
                 done = self._launch_uninstanced(device, view, g, radii, s, step)
@@ -1080,6 +1088,15 @@ class RasterBackend:
         return present
 
     # ------------------------------------------------------------------ parity exports
+    def export_reached(self, P, geom):
+        """[P] uint8 copy of the flags the last forward blend on `geom` left (GeomView.reached: the last P bytes' 256-B block of
+        the geometry buffer): 1 = the backward blend visits a list entry of this Gaussian.  Device library only."""
+        gb = self.scratch_bytes(P, 16, 16, 0)[0]
+        off = gb - ((P + 255) // 256) * 256
+        if geom.device.type == "cuda":
+            torch.cuda.current_stream(geom.device).synchronize()
+        return geom[off:off + P].clone()
+
     def export_state(self, P, W, H, R, geom, binning, img):
         """Plain-array copies of the forward's internal state (tests / debugging only)."""
         device = geom.device
