@@ -864,6 +864,58 @@ int gs_densify_stats(const int32_t* radii, const float* dL_dmeans2D /*[P,3]*/, i
                      float* max_radii2D /*[P]*/, float* xyz_gradient_accum /*[P]*/, float* denom /*[P]*/,
                      void* stream);
 
+/* ---- densify, split and prune as one re-layout on the device (gaussian_model.py:395-467; the host form and arbiter is
+ * GaussianModelLite.densify_and_prune).  Four steps, the host in between only to size the new buffers and draw the noise:
+ *
+ * gs_densify_plan (two launches): per row i of the P, from the raw scaling [P,3] and opacity [P] and the statistics [P],
+ *   g = xyz_gradient_accum / denom (NaN -> 0), max_scale = max_k exp(scaling_k), small = max_scale <= scale_bound, and one flag
+ *   byte: GS_DENSIFY_CLONE = |g| >= max_grad && small; GS_DENSIFY_SPLIT = g >= max_grad && !small; GS_DENSIFY_PRUNE_SELF =
+ *   sigmoid(opacity) < min_opacity || (size_test && max_scale > world_bound); GS_DENSIFY_PRUNE_SAMPLE = the same for the N
+ *   samples of the row, with max_k exp(log(exp(scaling_k) / sample_div)) in place of max_scale (sample_div = 0.8 N).  All five
+ *   thresholds are the fp32 values torch compares fp32 tensors with.  A row contributes: a survivor if it is neither split nor
+ *   PRUNE_SELF, a clone if it is a survivor and CLONE, N samples if it is SPLIT and not PRUNE_SAMPLE.
+ *   tmp (>= gs_densify_tmp_bytes(P) bytes, 256-byte aligned) receives, first, the GS_DENSIFY_COUNTS totals as uint32 -
+ *   [survivors, clones kept, split rows, split rows whose samples are kept, rows with CLONE] - then, from byte 256, the P flag
+ *   bytes; behind them the per-256-row-block counts and their exclusive prefixes over the blocks (private to gs_densify_emit).
+ * gs_densify_emit (one launch): for the output order [survivors | clones | sample block 0 | ... | sample block N-1], each group by
+ *   ascending source row, P2 = n_keep + n_clone_keep + N n_split_keep rows: table[j] = source row | kind << 30 (kind:
+ *   GS_DENSIFY_SURVIVOR / CLONED / SAMPLE) and new_xyz[j] = the row's centre - a copy of xyz for a survivor or a clone; for sample k
+ *   of the split row of rank r among ALL n_split split rows, R(q / |q|) (noise[k n_split + r] * exp(scaling)) + xyz with R of
+ *   general_utils.py:78-99 and noise [N n_split, 3].  The four counts are the first four totals of the plan in the same tmp: the
+ *   kernel compares them with what it finds there and writes nothing if they differ.
+ * gs_morton_codes (one launch): codes[i] = the 30-bit Morton code of xyz[i] in the box lo[3] .. hi[3] (device memory, fp32), 10 bits
+ *   per axis, q = clamp(rint((x - lo) / max(hi - lo, 1e-30) * 1023), 0, 1023) in float64, bits of x, y, z interleaved from bit 0.
+ * gs_densify_gather (one launch): output row j of the new flat parameter / exp_avg / exp_avg_sq buffers (field-major, nfields
+ *   blocks [P2, widths[f]]) from row e = perm ? perm[j] : j of the table: a survivor copies its source's parameters and both
+ *   moments bit for bit; a clone copies the parameters, moments +0; a sample likewise, except field xyz_field (width 3), which is
+ *   new_xyz[e] for every kind, and field scaling_field = log(exp(s) / sample_div).  A row whose perm or table entry is out of
+ *   range is left unwritten.  1 416 B of compulsory traffic per output row of 59 floats.
+ * GS_E_NULL: a required pointer is missing (noise only when n_split_keep > 0, perm never); GS_E_SHAPE: P < 1 or >= 2^30, N outside
+ * 1 .. GS_DENSIFY_MAX_N, counts that are negative, exceed P or do not add up to P2, P2 < 1, a field count or width out of range;
+ * GS_E_SCRATCH: tmp_bytes too small.  Everything is enqueued on `stream`; no host synchronisation, no atomics: the same inputs
+ * give the same bits. */
+#define GS_DENSIFY_CLONE 1
+#define GS_DENSIFY_SPLIT 2
+#define GS_DENSIFY_PRUNE_SELF 4
+#define GS_DENSIFY_PRUNE_SAMPLE 8
+#define GS_DENSIFY_SURVIVOR 0
+#define GS_DENSIFY_CLONED 1
+#define GS_DENSIFY_SAMPLE 2
+#define GS_DENSIFY_COUNTS 5
+#define GS_DENSIFY_MAX_N 8
+size_t gs_densify_tmp_bytes(int32_t P);
+int gs_densify_plan(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P,
+                    int32_t N, float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div,
+                    int32_t size_test, void* tmp, size_t tmp_bytes, void* stream);
+int gs_densify_emit(const void* tmp, size_t tmp_bytes, const float* xyz, const float* scaling, const float* rotation,
+                    const float* noise, int32_t P, int32_t N, int32_t n_keep, int32_t n_clone_keep, int32_t n_split,
+                    int32_t n_split_keep, int32_t P2, uint32_t* table, float* new_xyz, void* stream);
+int gs_morton_codes(const float* xyz, int64_t n, const float* lo, const float* hi, int32_t* codes, void* stream);
+int gs_densify_gather(const int64_t* perm, const uint32_t* table, const float* new_xyz, int32_t P2, const float* old_flat,
+                      const float* old_exp_avg, const float* old_exp_avg_sq, int32_t P, float* new_flat, float* new_exp_avg,
+                      float* new_exp_avg_sq, int32_t nfields, const int32_t* widths /*host*/, int32_t xyz_field,
+                      int32_t scaling_field, float sample_div, void* stream);
+
 /* ---- the visibility-sparse gradient exchange of the data-parallel step (N > 1; no reference counterpart: the reference trains
  * on one GPU).  Only Gaussians that emitted instances in SOME rank's view have a non-zero gradient row, so the ranks exchange
  * the rows of the union only.  The flat gradient buffer is field-major: field f is a [P, widths[f]] row-major block, the blocks

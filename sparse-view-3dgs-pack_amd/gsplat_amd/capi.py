@@ -223,6 +223,11 @@ PROTOTYPES = {
     "activations_fwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "activations_bwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "densify_stats": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P]),
+    "densify_tmp_bytes": (_SZ, [_I32]),
+    "densify_plan": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _F, _F, _F, _I32, _P, _SZ, _P]),
+    "densify_emit": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "morton_codes": (C.c_int, [_P, _I64, _P, _P, _P, _P]),
+    "densify_gather": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, C.POINTER(C.c_int32), _I32, _I32, _F, _P]),
     "profile_enable": (C.c_int, [_I32]),
     "profile_only": (C.c_int, [_I32]),
     "profile_reset": (C.c_int, []),
@@ -257,7 +262,10 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # DNGaussian's neural heads: restated in torch (tests/neural_reference.py)
                "dng_heads_tmp_bytes", "dng_heads_fwd", "dng_heads_bwd",
                # DNGaussian's per-Gaussian regulariser, view directions, near mask: restated in torch (tests/dng_reg_reference.py)
-               "dng_reg_tmp_bytes", "dng_reg_fwd", "dng_reg_bwd", "view_dirs_fwd", "view_dirs_bwd", "near_mask")
+               "dng_reg_tmp_bytes", "dng_reg_fwd", "dng_reg_bwd", "view_dirs_fwd", "view_dirs_bwd", "near_mask",
+               # densify / split / prune on the device: GaussianModelLite.densify_and_prune's host path is the arbiter
+               # (tests/densify_reference.py restates the plan in torch)
+               "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

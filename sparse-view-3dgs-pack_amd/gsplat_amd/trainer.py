@@ -593,7 +593,7 @@ class GaussianModelLite:
         return R.view(-1, 3, 3)
 
     def densify_and_prune(self, max_grad, min_opacity, extent, max_screen_size, radii=None, generator=None, N=2,
-                          decisions=None):
+                          decisions=None, on_device=False):
         """gaussian_model.py:395-467 in one re-layout: clone small Gaussians with a large view-space gradient,
         split large ones into N samples of their own distribution (scale / (0.8 N)), drop the split originals,
         then prune by opacity / world size.  Row order = the reference's: [survivors, clones, split samples].
@@ -607,7 +607,22 @@ class GaussianModelLite:
         decisions["replay"] = such a record, the recorded masks are USED instead of this model's own, and what this model
         would have decided is reported beside them (decisions["own"], decisions["disagree"]): two implementations whose
         statistics differ in the last bits take the same discrete trajectory, which separates threshold chaos from
-        arithmetic differences (tests/test_gpu_psnr_parity.py)."""
+        arithmetic differences (tests/test_gpu_psnr_parity.py).
+        `on_device` (default off): the same result from HIP kernels (csrc/gs_densify.hip, _densify_on_device) - the decisions
+        taken per row on the device, ONE host read-back (the counts that size the new buffers and the noise; the upload of the
+        CPU-drawn noise is the only other host wait), one gather pass
+        that writes parameters and moments in their final order, Morton order included.  Needs a GPU model with the flat Adam
+        state; copied values are the host path's bit for bit, the split samples' centres and scales agree to the last bits
+        (tests/test_gpu_densify_device.py).  With `decisions`, or when every row is pruned, the host path runs."""
+        if on_device:
+            api = getattr(self.optimizer, "api", None)
+            if not (self.flat.is_cuda and isinstance(self.optimizer, FlatAdam) and hasattr(api, "_densify_plan")):
+                raise RuntimeError("densify_and_prune(on_device=True) needs a GPU model built with the HIP api (flat Adam state); "
+                                   "there is no fallback")
+            if decisions is None:
+                out = self._densify_on_device(max_grad, min_opacity, extent, max_screen_size, generator, N)
+                if out is not None:
+                    return out
         with torch.no_grad():
             P0 = self.P
             grads = self.xyz_gradient_accum / self.denom
@@ -677,6 +692,64 @@ class GaussianModelLite:
             self.denom = torch.zeros((self.P, 1), device=self.device)
             self.max_radii2D = torch.zeros((self.P,), device=self.device)
             return int(ci.numel()), ns, int(prune.sum())
+
+    def _densify_on_device(self, max_grad, min_opacity, extent, max_screen_size, generator, N):
+        """densify_and_prune from the kernels of csrc/gs_densify.hip (include/gsplat.h: gs_densify_plan / emit / gather,
+        gs_morton_codes).  Returns (n_clone, n_split, n_pruned), or None - nothing written, the generator untouched - when every
+        row would be pruned (the caller then takes the host path)."""
+        import ctypes as C
+        opt = self.optimizer
+        api, dev, P0 = opt.api, self.flat.device, self.P
+        stream = _stream_of(self.flat)
+        with torch.no_grad():
+            raw = {name: self.params[name].detach() for name, _ in self.fields}
+            accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
+            if accum.numel() != P0 or denom.numel() != P0 or accum.dtype != torch.float32 or denom.dtype != torch.float32:
+                raise RuntimeError("densification statistics do not match the model")
+            # torch compares fp32 tensors with Python floats by rounding the scalar to fp32 ONCE: the products are formed in
+            # double as the host path forms them, then every threshold is rounded
+            f32 = lambda v: C.c_float(v).value   # noqa: E731
+            sample_div = f32(0.8 * N)
+            nbytes = api.raw("densify_tmp_bytes")(P0)
+            tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+            api.call("densify_plan", raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(), P0, N,
+                     f32(max_grad), f32(self.percent_dense * extent), f32(min_opacity), f32(0.1 * extent), sample_div,
+                     1 if max_screen_size else 0, tmp.data_ptr(), nbytes, stream)
+            # the ONE read-back: the counts size the new buffers and the noise (whose upload below blocks too, when rows split)
+            n_keep, n_clone_keep, ns, ns_keep, n_clone = tmp[:20].view(torch.int32).cpu().tolist()
+            P2 = n_keep + n_clone_keep + N * ns_keep
+            if P2 == 0:
+                return None
+            noise = None
+            if ns:
+                if generator is None:
+                    generator = torch.Generator().manual_seed(0)
+                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
+            table = torch.empty((P2,), dtype=torch.int32, device=dev)
+            new_xyz = torch.empty((P2, 3), dtype=torch.float32, device=dev)
+            api.call("densify_emit", tmp.data_ptr(), nbytes, raw["xyz"].data_ptr(), raw["scaling"].data_ptr(),
+                     raw["rotation"].data_ptr(), None if noise is None else noise.data_ptr(), P0, N, n_keep, n_clone_keep, ns,
+                     ns_keep, P2, table.data_ptr(), new_xyz.data_ptr(), stream)
+            perm = None
+            if getattr(self, "spatial_order", False):   # synthetic.morton_order of the new centres, no read-back
+                lo, hi = torch.aminmax(new_xyz, dim=0)
+                codes = torch.empty((P2,), dtype=torch.int32, device=dev)
+                api.call("morton_codes", new_xyz.data_ptr(), P2, lo.data_ptr(), hi.data_ptr(), codes.data_ptr(), stream)
+                perm = torch.sort(codes, stable=True).indices
+            old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
+            names = [name for name, _ in self.fields]
+            widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
+            self._allocate(P2)
+            opt.alloc_moments()
+            api.call("densify_gather", None if perm is None else perm.data_ptr(), table.data_ptr(), new_xyz.data_ptr(), P2,
+                     old_flat.data_ptr(), old_m.data_ptr(), old_v.data_ptr(), P0, self.flat.data_ptr(), opt.exp_avg.data_ptr(),
+                     opt.exp_avg_sq.data_ptr(), len(names), widths, names.index("xyz"), names.index("scaling"), sample_div, stream)
+            for p in self.params.values():  # replaced tensors have no gradient until the next backward
+                p.grad = None
+            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+            self.denom = torch.zeros((self.P, 1), device=self.device)
+            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            return n_clone, ns, (P0 - ns - n_keep) + (n_clone - n_clone_keep) + N * (ns - ns_keep)
 
     def proximity(self, extent, api=None):
         """FSGS's proximity-guided unpooling (FSGS/scene/gaussian_model.py:405-420, N = 3), the reference's tensor
@@ -938,6 +1011,7 @@ class TrainOptions:
         self.random_background = False    # arguments/__init__.py: a fresh torch.rand(3) background every iteration (train.py:117)
         self.cameras_extent = 1.0         # scene.cameras_extent = getNerfppNorm radius (dataset_readers.py:48-69)
         self.seed = 0
+        self.densify_on_device = False    # densify_and_prune(on_device=True): the HIP form (GPU models only)
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option %s" % k)
@@ -1075,7 +1149,8 @@ class Trainer:
             # (densify_decisions: parity instrument, see GaussianModelLite.densify_and_prune - a callable iteration -> dict)
             dec = self.densify_decisions(iteration) if self.densify_decisions is not None else None
             densified = m.densify_and_prune(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, thr,
-                                            self.last["radii"], generator=gen, decisions=dec)
+                                            self.last["radii"], generator=gen, decisions=dec,
+                                            on_device=bool(getattr(opt, "densify_on_device", False)))
         if will_reset:
             m.reset_opacity()
             reset = True
