@@ -395,6 +395,11 @@ int gso_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const
                   float b1, float b2, float eps, int32_t step, void*) {
   return gso_adam_step_masked(p, g, m, v, n, segs, nseg, b1, b2, eps, step, nullptr, nullptr, nullptr);
 }
+/* gs_adam_step_gated: *gate != 0 - nobody steps */
+int gso_adam_step_gated(float* p, const float* g, float* m, float* v, int64_t n, const GsAdamSeg* segs, int32_t nseg,
+                        float b1, float b2, float eps, int32_t step, const float* gate, void*) {
+  return gso_adam_step_masked(p, g, m, v, n, segs, nseg, b1, b2, eps, step, gate, nullptr, nullptr);
+}
 /* + "sparse_adam" (LGDWT-GS/train.py:282-284: visible = radii > 0; optimizer.step(visible, N)): rows with row_mask <= 0 keep
  * parameters and moments; gate != 0: nobody steps (data-parallel validity flag) */
 int gso_adam_step_masked(float* p, const float* g, float* m, float* v, int64_t n, const GsAdamSeg* segs, int32_t nseg,

@@ -28,7 +28,7 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _make(rank, world, fused, nir=False):
+def _make(rank, world, fused, nir=False, P=30000, W=480, H=320):
     import diff_gaussian_rasterization as dgr
     import lgdwt_loss
     from gsplat_amd import hip_backend, synthetic
@@ -37,7 +37,6 @@ def _make(rank, world, fused, nir=False):
     from simple_knn._C import distCUDA2
     dev = torch.device("cuda", 0)
     hip = hip_backend()
-    P, W, H = 30000, 480, 320
     sc = synthetic.trained_like(P, seed=3, sh_degree=3, knn=lambda x: distCUDA2(x.to(dev)).cpu())
     cams = [camera_to(c, dev) for c in synthetic.orbit_cameras(W, H)[:4]]
     g = torch.Generator().manual_seed(5)
@@ -62,12 +61,12 @@ def _make(rank, world, fused, nir=False):
     return tr, hip
 
 
-def _worker(rank, world, port, outdir, mode, sharded, nir=False):
+def _worker(rank, world, port, outdir, mode, sharded, nir=False, size=(30000, 480, 320)):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    tr, hip = _make(rank, world, fused=(mode != "plain"), nir=nir)
+    tr, hip = _make(rank, world, fused=(mode != "plain"), nir=nir, P=size[0], W=size[1], H=size[2])
     tr.sharded_optimizer, tr.sparse_exchange = sharded is True, sharded == "sparse"
     hip.tile_cull = True
     info = {}
@@ -83,7 +82,7 @@ def _worker(rank, world, port, outdir, mode, sharded, nir=False):
         tr.sync()
         if mode == "sabotage" and rank == 1:
             # rank 1's next camera (index 1): its limits now cut everything
-            hip.camera_entry(480, 320, camera_key=("trainer", tr.uid, tr.camera_index(4)))["limit"].fill_(1e-3)
+            hip.camera_entry(size[1], size[2], camera_key=("trainer", tr.uid, tr.camera_index(4)))["limit"].fill_(1e-3)
         before = tr.model.flat.detach().clone()
         t_before = tr.model.optimizer.t
         tr.step(4)
@@ -109,10 +108,10 @@ def _worker(rank, world, port, outdir, mode, sharded, nir=False):
     dist.destroy_process_group()
 
 
-def _run(mode, sharded, nir=False):
+def _run(mode, sharded, nir=False, size=(30000, 480, 320)):
     world = 2
     with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_worker, args=(world, _free_port(), d, mode, sharded, nir), nprocs=world, join=True)
+        mp.spawn(_worker, args=(world, _free_port(), d, mode, sharded, nir, size), nprocs=world, join=True)
         return [torch.load(os.path.join(d, "%s_rank%d.pt" % (mode, r))) for r in range(world)]
 
 
@@ -159,6 +158,21 @@ def test_fused_data_parallel_step_is_the_plain_one_and_a_bad_view_repeats_on_eve
         ex = fused[0]["exchange"]
         print("sparse exchange:", ex)
         assert 0 < ex["union_rows"] < 0.8 * ex["rows"] and ex["sparse_bytes"] < 0.85 * ex["dense_bytes"]
+
+
+def test_fused_data_parallel_step_off_the_float4_grid():
+    """P = 1021 at 96 x 64: the gradient views into the flat gradient buffer (features at 3 P floats, opacity at 51 P, ...) start
+    off 16 bytes, so the gradients-out form writes every row array element by element (grad_block's second body).  The fused
+    data-parallel step against the plain one, as the 30 000-row case above compares them."""
+    size = (1021, 96, 64)
+    plain = _run("plain", False, size=size)
+    fused = _run("fused", False, size=size)
+    for run in (plain, fused):
+        for k in ("flat", "accum", "denom", "maxr", "m1"):
+            assert torch.equal(run[0][k], run[1][k]), "replicas differ in " + k
+        assert run[0]["t"] == run[1]["t"] == 8 and run[0]["flat"].numel() == 1021 * 59
+    _same_run(plain[0], fused[0])
+    assert float(fused[0]["m1"].abs().max()) > 0 and float(fused[0]["denom"].max()) >= 2
 
 
 @pytest.mark.timeout(900)
