@@ -955,6 +955,37 @@ int gs_exposure_adam(const float* partials, int64_t n_partials, int32_t camera, 
  * so the union of the ranks' masks can be exchanged while the loss and the backward are still running). */
 int gs_export_row_mask(const GsScratch* scratch, int32_t P, uint8_t* mask, void* stream);
 
+/* ---- test-set evaluation of one view (csrc/gs_eval.hip): MSE / PSNR, SSIM and L1 of render against gt, both [C,H,W] fp32,
+ * in the forms of the reference's evaluation scripts, from one pass over the images and a one-workgroup combine ----
+ * The pixel transform, applied to BOTH images while they are staged, in this order:
+ *   GS_EVAL_CLAMP     x <- clamp(x, 0, 1)                                     (training_report, DNGaussian/train_llff.py:298,302)
+ *   GS_EVAL_QUANTISE  q = (uint8) clamp(x * 255 + 0.5, 0, 255), x <- q / 255  (torchvision save_image -> to_tensor: the PNG
+ *                     round trip of LGDWT-GS/render.py:45-46 -> metrics.py:31-32; the multiply and the add round separately)
+ *   GS_EVAL_MASK_DTU  x <- x * m + (1 - m), mask [H,W] fp32 broadcast over the channels (DNGaussian/metrics_dtu.py:40-46;
+ *                     the reference's mask is a 3-channel image, DTU's are grey).  SSIM and L1 run over all pixels of the
+ *                     blended images (zero padding outside the image, as F.conv2d pads after the blend), MSE / PSNR over
+ *                     the elements with m == 1 only (metrics_dtu.py:93-95).
+ * out_row[GS_EVAL_WORDS] doubles in device memory: 0 mse | 1 psnr = 20 log10(1 / sqrt(mse)) | 2 ssim (mean of the map, 11-tap
+ * Gaussian window, constants C1, C2) | 3 l1 (mean) | 4 count = the elements mse ran over | 5..7 reserved = 0.  Identical images:
+ * psnr = +inf; an empty mask: mse = psnr = NaN, count = 0 - both as in the reference.
+ * quantised_out (nullable): uint8 [H,W,C], the bytes save_image would write for render (before any mask; the same bytes
+ * with or without GS_EVAL_CLAMP / GS_EVAL_QUANTISE).
+ * tmp: >= gs_eval_tmp_bytes(C, H, W) bytes of device scratch, one row of gs_eval_partials_count(C, H, W) float64 partials per
+ * sum; every partial is written before it is read.  The error sums and the count accumulate in float64, the SSIM-map sum of
+ * a workgroup in fp32 as the criterion's kernels do; the partials are added in index order in float64: the same bits on
+ * every run.  Two launches on `stream`, no atomics, no host synchronisation, no device-to-host copy.
+ * GS_E_NULL: render, gt, tmp or out_row missing, or GS_EVAL_MASK_DTU without mask; GS_E_SHAPE: C, H or W <= 0, C > 4, unknown
+ * flag bits, or tmp_bytes too small.  Both size queries return 0 for such a shape. */
+#define GS_EVAL_CLAMP 1
+#define GS_EVAL_QUANTISE 2
+#define GS_EVAL_MASK_DTU 4
+#define GS_EVAL_WORDS 8
+int64_t gs_eval_partials_count(int32_t C, int32_t H, int32_t W);
+size_t gs_eval_tmp_bytes(int32_t C, int32_t H, int32_t W);
+int gs_eval_metrics(const float* render, const float* gt, const float* mask /*NULL unless GS_EVAL_MASK_DTU*/, int32_t C,
+                    int32_t H, int32_t W, int32_t flags, float C1, float C2, void* tmp, size_t tmp_bytes,
+                    double* out_row /*[GS_EVAL_WORDS], device*/, uint8_t* quantised_out /*NULL ok*/, void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

@@ -241,6 +241,9 @@ PROTOTYPES = {
     "image_stage_fwd": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P]),
     "image_stage_bwd": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "exposure_adam": (C.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _I32, _F, C.c_double, C.c_double, _F, _I32, _P, _P]),
+    "eval_partials_count": (C.c_int64, [_I32, _I32, _I32]),
+    "eval_tmp_bytes": (_SZ, [_I32, _I32, _I32]),
+    "eval_metrics": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _SZ, _P, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -265,7 +268,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                "dng_reg_tmp_bytes", "dng_reg_fwd", "dng_reg_bwd", "view_dirs_fwd", "view_dirs_bwd", "near_mask",
                # densify / split / prune on the device: GaussianModelLite.densify_and_prune's host path is the arbiter
                # (tests/densify_reference.py restates the plan in torch)
-               "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather")
+               "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather",
+               # test-set evaluation (PSNR / SSIM / L1 per view): restated in torch (tests/eval_reference.py)
+               "eval_partials_count", "eval_tmp_bytes", "eval_metrics")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

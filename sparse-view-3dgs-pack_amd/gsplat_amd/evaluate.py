@@ -1,0 +1,183 @@
+"""Test-set evaluation over libgsplat_hip.so (csrc/gs_eval.hip): PSNR, SSIM and L1 of a render against its ground truth
+from one pass over the two images, in the forms the reference's evaluation computes them.
+
+  metrics.py (render.py's PNGs read back)     image_metrics(render, gt, quantise=True)          LGDWT-GS/metrics.py:31-32,70-83
+  training_report (clamped tensors)           image_metrics(render, gt, clamp=True)             DNGaussian/train_llff.py:298-302
+  metrics_dtu.py (white outside the mask)     image_metrics(render, gt, mask=m, quantise=True)  DNGaussian/metrics_dtu.py:40-46,93-95
+
+The pixel transform runs in this order on both images: clamp to [0, 1], the 8-bit round trip of torchvision's save_image /
+to_tensor, the blend to white under the mask.  Divergences from the reference, all raised or documented: one view per call
+(the reference-named psnr / ssim loop over a batch), fp32 CUDA(HIP) tensors only, at most 4 channels, the DTU mask is ONE
+[H,W] plane broadcast over the channels (the reference's is a 3-channel image; DTU's masks are grey), images arrive at the
+mask's size (no Image.resize), no LPIPS, no SSIM_sk, no PNG encoding (the bytes are offered).
+
+Nothing here synchronises with the host: a view's numbers are float64 words in device memory, and Evaluator.result() is the
+one read-back of a whole test set."""
+import ctypes as C
+
+import torch
+
+from ._lib import hip_api
+from .io import write_results_json  # noqa: F401  (the evaluation's files: results.json, per_view.json)
+
+CLAMP, QUANTISE, MASK_DTU = 1, 2, 4  # GS_EVAL_CLAMP, GS_EVAL_QUANTISE, GS_EVAL_MASK_DTU
+WORDS = 8                            # GS_EVAL_WORDS: mse, psnr, ssim, l1, count, 3 reserved
+C1, C2 = 0.01 ** 2, 0.03 ** 2        # utils/loss_utils.py (_ssim)
+_MSE, _PSNR, _SSIM, _L1, _COUNT = range(5)
+
+
+def _stream(t):
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _image(t, what):
+    """[C,H,W] or [1,C,H,W] -> contiguous [C,H,W]"""
+    if not torch.is_tensor(t):
+        raise ValueError("%s: expected a tensor, got %s" % (what, type(t).__name__))
+    if t.dim() == 4:
+        if t.shape[0] != 1:
+            raise ValueError("%s: batch 1 only (got batch %d) - call it once per view" % (what, t.shape[0]))
+        t = t[0]
+    if t.dim() != 3:
+        raise ValueError("%s: expected a [C,H,W] or [1,C,H,W] image, got shape %s" % (what, tuple(t.shape)))
+    if not t.is_cuda:
+        raise ValueError("%s: CUDA(HIP) tensors only - there is no CPU path" % what)
+    if t.dtype != torch.float32:
+        raise ValueError("%s: fp32 only (got %s)" % (what, t.dtype))
+    return t.contiguous()
+
+
+def _check(render, gt, mask):
+    render, gt = _image(render, "render"), _image(gt, "gt")
+    if render.shape != gt.shape:
+        raise ValueError("render %s and gt %s differ in shape" % (tuple(render.shape), tuple(gt.shape)))
+    if gt.device != render.device:
+        raise ValueError("render and gt live on different devices")
+    Cn, H, W = (int(x) for x in render.shape)
+    if Cn > 4 or min(Cn, H, W) < 1:
+        raise ValueError("1 to 4 channels of at least one pixel (got %s)" % (tuple(render.shape),))
+    if mask is not None:
+        if not torch.is_tensor(mask) or not mask.is_cuda or mask.dtype != torch.float32 or mask.device != render.device:
+            raise ValueError("mask: an fp32 CUDA(HIP) tensor on the images' device")
+        if mask.numel() != H * W or tuple(mask.shape[-2:]) != (H, W):
+            raise ValueError("mask: one [H,W] plane of the images' size (got %s for %dx%d)" % (tuple(mask.shape), H, W))
+        mask = mask.reshape(H, W).contiguous()
+    return render, gt, mask, Cn, H, W
+
+
+def _flags(mask, clamp, quantise):
+    return (CLAMP if clamp else 0) | (QUANTISE if quantise else 0) | (MASK_DTU if mask is not None else 0)
+
+
+def _launch(render, gt, mask, Cn, H, W, flags, tmp, row, quantised):
+    hip_api().call("eval_metrics", render.data_ptr(), gt.data_ptr(), None if mask is None else mask.data_ptr(), Cn, H, W,
+                   int(flags), C1, C2, tmp.data_ptr(), tmp.numel(), row.data_ptr(),
+                   None if quantised is None else quantised.data_ptr(), _stream(render))
+
+
+def _tmp(device, Cn, H, W):
+    return torch.empty((int(hip_api().raw("eval_tmp_bytes")(Cn, H, W)),), dtype=torch.uint8, device=device)
+
+
+def image_metrics(render, gt, mask=None, clamp=False, quantise=False, return_bytes=False):
+    """-> {"mse", "psnr", "ssim", "l1", "count"}: 0-d float64 device tensors (views of one row), plus "bytes" - the uint8
+    [H,W,C] image torchvision's save_image would write for `render` - when return_bytes.  Identical images give
+    psnr = +inf; an empty mask gives mse = psnr = NaN, as in the reference."""
+    render, gt, mask, Cn, H, W = _check(render, gt, mask)
+    dev = render.device
+    row = torch.empty((WORDS,), dtype=torch.float64, device=dev)
+    q = torch.empty((H, W, Cn), dtype=torch.uint8, device=dev) if return_bytes else None
+    _launch(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), _tmp(dev, Cn, H, W), row, q)
+    out = {"mse": row[_MSE], "psnr": row[_PSNR], "ssim": row[_SSIM], "l1": row[_L1], "count": row[_COUNT]}
+    if return_bytes:
+        out["bytes"] = q
+    return out
+
+
+def _views(img1, img2):
+    if img1.dim() == 3:
+        img1, img2 = img1[None], img2[None]
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError("expected two [B,C,H,W] (or [C,H,W]) images of one shape, got %s and %s"
+                         % (tuple(img1.shape), tuple(img2.shape)))
+    return img1, img2
+
+
+def psnr(img1, img2):
+    """utils/image_utils.py:17-19: [B,1] (float32, as the reference's), one kernel pass per view."""
+    img1, img2 = _views(img1, img2)
+    return torch.stack([image_metrics(a, b)["psnr"] for a, b in zip(img1, img2)]).to(torch.float32)[:, None]
+
+
+def ssim(img1, img2, window_size=11, size_average=True):
+    """utils/loss_utils.py ssim with its defaults: a scalar (float32), the mean over the whole batch.  No gradient: this is
+    the evaluation's SSIM (the training loss is fused_ssim / lgdwt_loss)."""
+    if window_size != 11 or not size_average:
+        raise ValueError("ssim: window_size 11 and size_average=True only")
+    img1, img2 = _views(img1, img2)
+    return torch.stack([image_metrics(a, b)["ssim"] for a, b in zip(img1, img2)]).mean().to(torch.float32)
+
+
+class Evaluator:
+    """The [n_views, 8] float64 device table of a test set and the scratch of its one image size.  add() writes a row with two
+    launches and no host wait; result() is the one read-back."""
+    FILL = float("nan")   # rows no view was added to
+
+    def __init__(self, n_views, C, H, W, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("Evaluator: CUDA(HIP) device only - there is no CPU path")
+        if n_views < 1 or not 1 <= C <= 4 or H < 1 or W < 1:
+            raise ValueError("Evaluator: n_views >= 1, 1..4 channels, H, W >= 1 (got %r)" % ((n_views, C, H, W),))
+        self.shape = (int(C), int(H), int(W))
+        self.table = torch.full((int(n_views), WORDS), self.FILL, dtype=torch.float64, device=device)
+        self.tmp = _tmp(device, *self.shape)   # (views are added on one stream: the launches of two views never overlap)
+
+    def add(self, i, render, gt, mask=None, clamp=False, quantise=False):
+        """Row i <- the metrics of this view."""
+        if not 0 <= int(i) < self.table.shape[0]:
+            raise ValueError("Evaluator.add: view %d outside 0..%d" % (i, self.table.shape[0] - 1))
+        render, gt, mask, Cn, H, W = _check(render, gt, mask)
+        if (Cn, H, W) != self.shape or render.device != self.table.device:
+            raise ValueError("Evaluator.add: view is %s on %s, the table was built for %s on %s"
+                             % ((Cn, H, W), render.device, self.shape, self.table.device))
+        _launch(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), self.tmp, self.table[int(i)], None)
+
+    def result(self, names=None):
+        """The one read-back -> {"SSIM", "PSNR", "L1", "per_view": {"SSIM": {name: v}, "PSNR": {...}, "L1": {...}}}.  The means
+        are plain means of the per-view values (metrics.py:76-83: torch.tensor(psnrs).mean())."""
+        table = self.table.cpu()
+        n = table.shape[0]
+        names = ["%05d.png" % i for i in range(n)] if names is None else list(names)   # render.py:45 names its files so
+        if len(names) != n:
+            raise ValueError("%d names for %d views" % (len(names), n))
+        out, per = {}, {}
+        for key, col in (("SSIM", _SSIM), ("PSNR", _PSNR), ("L1", _L1)):
+            vals = [float(v) for v in table[:, col]]
+            out[key] = sum(vals) / n
+            per[key] = dict(zip(names, vals))
+        out["per_view"] = per
+        return out
+
+
+def evaluate_views(model, cameras, gts, Rasterizer, Settings, bg, names=None, quantise=True, clamp=True, masks=None,
+                   camera_keys=None):
+    """Render every camera of a test set and score it against its ground truth -> Evaluator.result(names).
+    The renders go through trainer.render (the plain forward: no exposure, no clamp - the metric kernel clamps), under
+    no_grad.  No metric is read back between views; the rasterizer's own wait for a view's instance count is all the host
+    waits for.  camera_keys: one key per camera for the backend's per-camera state (GaussianRasterizer.camera_key; depth
+    limits stay off), default ("evaluate", i)."""
+    from .trainer import render
+    if len(cameras) != len(gts) or len(cameras) == 0:
+        raise ValueError("evaluate_views: %d cameras and %d ground-truth images" % (len(cameras), len(gts)))
+    if masks is not None and len(masks) != len(cameras):
+        raise ValueError("evaluate_views: %d masks for %d cameras" % (len(masks), len(cameras)))
+    ev = None
+    with torch.no_grad():
+        for i, (cam, gt) in enumerate(zip(cameras, gts)):
+            key = ("evaluate", i) if camera_keys is None else camera_keys[i]
+            img = render(cam, model, Rasterizer, Settings, bg, filter_as_indices=None, clamp=False, camera_key=key)["render"]
+            if ev is None:
+                ev = Evaluator(len(cameras), img.shape[0], img.shape[1], img.shape[2], img.device)
+            ev.add(i, img, gt, mask=None if masks is None else masks[i], clamp=clamp, quantise=quantise)
+    return ev.result(names)

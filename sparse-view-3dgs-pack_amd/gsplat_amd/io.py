@@ -493,3 +493,17 @@ def write_cameras_json(path, cam_infos):
     """scene/__init__.py:62-70: cameras.json next to the model."""
     with open(path, "w") as f:
         json.dump([camera_to_json(i, c) for i, c in enumerate(cam_infos)], f)
+
+
+# ------------------------------------------------------------------------------------------------ evaluation results
+def write_results_json(model_path, method, result):
+    """results.json = {method: {"SSIM": ..., "PSNR": ...}} and per_view.json = {method: {"SSIM": {name: v}, ...}} under
+    model_path, in the nesting of metrics.py:85-88 (json.dump(..., indent=True)).  The keys are those of `result`: no
+    LPIPS key is written (absent, not zero); L1 is this package's addition."""
+    per = result["per_view"]
+    full = {k: v for k, v in result.items() if k != "per_view"}
+    os.makedirs(model_path, exist_ok=True)
+    with open(os.path.join(model_path, "results.json"), "w") as fp:
+        json.dump({method: full}, fp, indent=True)
+    with open(os.path.join(model_path, "per_view.json"), "w") as fp:
+        json.dump({method: per}, fp, indent=True)

@@ -1255,6 +1255,33 @@ class Trainer:
         be = getattr(getattr(self.Rasterizer, "_fn", None), "_impl", None)
         return getattr(be, "backend", None)
 
+    # what a plain forward leaves on the backend besides its own cameras' entries: put back after an evaluation
+    _EVAL_KEEPS = ("_capacity_hint", "_capacity_hint_limited", "_last", "last_workspace", "_pinned", "deferred",
+                   "last_deferred_num_rendered")
+
+    def evaluate(self, cameras=None, gts=None, **kw):
+        """PSNR / SSIM / L1 of the trainer's model over a test set (default: its own cameras and ground truth) ->
+        gsplat_amd.evaluate.evaluate_views' result; kw: names, quantise, clamp, masks.
+
+        Training state is left alone, and this is how: the pending verdict of the last step is settled first (sync);
+        every view is rendered through the PLAIN forward under no_grad, named ("trainer", uid, "eval", i) with
+        camera_limits off - so the per-camera entries of the training cameras (tile order, depth limits, the buffers a
+        captured graph holds) are neither read nor written, and the evaluation's own entries go when the trainer does;
+        the backend's capacity hints and last-forward records are restored afterwards.  No fused step is armed, no
+        optimizer counter, running mean or random stream is touched."""
+        from .evaluate import evaluate_views
+        self.sync()
+        cameras = self.cameras if cameras is None else cameras
+        gts = self.gts if gts is None else gts
+        be = self._backend()
+        saved = {k: getattr(be, k) for k in self._EVAL_KEEPS if be is not None and hasattr(be, k)}
+        try:
+            return evaluate_views(self.model, cameras, gts, self.Rasterizer, self.Settings, self.bg,
+                                  camera_keys=[("trainer", self.uid, "eval", i) for i in range(len(cameras))], **kw)
+        finally:
+            for k, v in saved.items():
+                setattr(be, k, v)
+
     # The single-GPU fused step without the autograd engine: its graph is two custom nodes in a row (rasterizer, criterion) whose
     # gradients end inside gs_backward_step, so the step calls their forward / backward bodies itself (a stand-in context
     # object each) - no graph construction, no engine thread hand-off: ~0.15 ms less host time per step, which is what
