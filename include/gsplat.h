@@ -265,6 +265,25 @@ int gs_backward_fsgs(const GsView* view, const GsGaussians* g, const int32_t* ra
                      const float* dL_ddepth, const float* dL_dalpha, const GsGrads* grads,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* The depth-only pass: the depth and alpha images of the generation above without its colour image, and their gradients
+ * with respect to the means and / or the opacities only - what DNGaussian's two depth passes (render_for_depth, render_for_opa:
+ * constant colour 1, scales and rotations detached) read.  Additive; device library only.
+ * gs_depth_forward runs on scratch whose geometry phase has run (gs_forward_geometry with antialiasing = 0 and any [P,3] array
+ * as colors_precomp: the colours are never read here), builds the lists unless scratch->binned, blends and leaves the
+ * backward blend's launch order.  out_depth / out_alpha [H,W] are the images of gs_forward_render_fsgs, bit for bit.
+ * Depth-limited lists, tile-order hints and exports are not served (tile_depth_limit set: GS_E_UNSUPPORTED).
+ * gs_depth_backward: dL_ddepth / dL_dalpha [H,W], either may be NULL (= zero).  grad_flags: 1 = means (dL_dmeans3D [P,3] and
+ * dL_dmeans2D [P,3], both required), 2 = opacities (dL_dopacity [P]), 3 = both; every row of a requested output is written.
+ * workspace: >= P * 128 bytes rounded up to 256 (the float64 blend sums), device memory.
+ * Status codes, no launch: anti-aliasing, raw_activations, shs_rest, extra_channel -> GS_E_UNSUPPORTED; NULL outputs or a NULL
+ * gradient pointer of a requested family -> GS_E_NULL; grad_flags outside 1..3 -> GS_E_SHAPE.  P == 0: outputs zeroed, GS_OK. */
+int gs_depth_forward(const GsView* view, const GsGaussians* g, GsScratch* scratch, float* out_depth,
+                     float* out_alpha, void* stream);
+int gs_depth_backward(const GsView* view, const GsGaussians* g, const int32_t* radii,
+                      const GsScratch* scratch, int64_t num_rendered, const float* dL_ddepth,
+                      const float* dL_dalpha, int grad_flags, float* dL_dmeans3D, float* dL_dmeans2D,
+                      float* dL_dopacity, void* workspace, size_t workspace_bytes, void* stream);
+
 /* present[i] = (view-space z of means3D[i]) > 0.2   (rasterizer_impl.cu:54-66) */
 int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix,
                     const float* projmatrix, uint8_t* present, void* stream);

@@ -597,6 +597,121 @@ int gs_backward_from_rows(const GsView* v, const GsGaussians* g, const int32_t* 
   return GS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the depth-only pass (gs_depth_pass.hip)
+// ------------------------------------------------------------------------------------------------
+static int depth_pass_args(const GsView* v, const GsGaussians* g) {
+  if (!v || !g) return GS_E_NULL;
+  if (v->antialiasing) return GS_E_UNSUPPORTED;  // the FSGS rasterizer generation has no anti-aliasing
+  if (g->raw_activations || g->shs_rest || g->extra_channel) return GS_E_UNSUPPORTED;
+  return check_args(v, g);
+}
+
+int gs_depth_forward(const GsView* v, const GsGaussians* g, GsScratch* sc, float* out_depth, float* out_alpha, void* stream) {
+  if (v && v->antialiasing) return GS_E_UNSUPPORTED;
+  if (!out_depth || !out_alpha) return GS_E_NULL;
+  int rc = depth_pass_args(v, g);
+  if (rc) return rc;
+  if (!sc || !sc->geom || !sc->img) return GS_E_NULL;
+  if (sc->tile_depth_limit || sc->tile_depth_limit_out) return GS_E_UNSUPPORTED;  // depth-limited lists are not served
+  hipStream_t s = (hipStream_t)stream;
+  const int P = g->P, W = v->image_width, H = v->image_height;
+  int gx, gy;
+  tile_grid(v, gx, gy);
+  const size_t T = (size_t)gx * gy, N = (size_t)W * H;
+  if (sc->img_bytes < img_bytes(N, T)) return GS_E_SCRATCH;
+  if (P == 0) {
+    GS_HIP_CHECK(hipMemsetAsync(out_depth, 0, sizeof(float) * N, s));
+    GS_HIP_CHECK(hipMemsetAsync(out_alpha, 0, sizeof(float) * N, s));
+    return GS_OK;
+  }
+  if (sc->geom_bytes < geom_bytes((size_t)P)) return GS_E_SCRATCH;
+  const int64_t cap = sc->binning_capacity;
+  if (cap < 0) return GS_E_SHAPE;
+  if (cap > 0 && (!sc->binning || sc->binning_bytes < bin_bytes((size_t)cap, T))) return GS_E_SCRATCH;
+  if (cap > 0xFFFFFFFFll) return GS_E_UNSUPPORTED;
+  GeomView gv = geom_view(sc->geom, (size_t)P);
+  ImgView iv = img_view(sc->img, N, T);
+  SortBufs bv = sort_view(sc->binning, (size_t)cap);
+  if (!sc->binned) {
+    rc = forward_bin_stage(v, sc, gv, iv, bv, P, gx, gy, s);
+    if (rc) return rc;
+  }
+  {
+    GS_PROF(ST_RENDER_FWD, s);
+    launch_depth_fwd(iv.ranges, bv.vals[0], W, H, gx, gy, gv.splat, iv.final_T, iv.n_contrib, iv.tile_work, iv.tile_stop_depth,
+                     out_depth, out_alpha, v->tile_cull ? 0 : 1, s);
+  }
+  {  // the backward blend's launch order, inline (nothing is exported to a camera's hints)
+    GS_PROF(ST_TILE_ORDER, s);
+    launch_tile_order(iv.tile_work, iv.tile_order, (int)T, nullptr, iv.tile_stop_depth, nullptr, gx, gy, gv.hdr, s);
+  }
+  GS_LAUNCH_CHECK(s, v->debug);
+  return GS_OK;
+}
+
+int gs_depth_backward(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc, int64_t num_rendered,
+                      const float* dL_ddepth, const float* dL_dalpha, int grad_flags, float* dL_dmeans3D, float* dL_dmeans2D,
+                      float* dL_dopacity, void* workspace, size_t workspace_bytes, void* stream) {
+  if (v && v->antialiasing) return GS_E_UNSUPPORTED;
+  if (grad_flags < 1 || grad_flags > 3) return GS_E_SHAPE;
+  if (((grad_flags & 1) && (!dL_dmeans3D || !dL_dmeans2D)) || ((grad_flags & 2) && !dL_dopacity)) return GS_E_NULL;
+  int rc = depth_pass_args(v, g);
+  if (rc) return rc;
+  if (!sc) return GS_E_NULL;
+  const int P = g->P, W = v->image_width, H = v->image_height;
+  if (P == 0) return GS_OK;
+  if (!radii || !sc->geom || !sc->img || !workspace) return GS_E_NULL;
+  if (workspace_bytes < gs_align((size_t)P * GR_ROW_BYTES)) return GS_E_SCRATCH;  // the float64 rows; no records
+  if (num_rendered < 0 || num_rendered > sc->binning_capacity) return GS_E_SHAPE;
+  if (num_rendered > 0 && !sc->binning) return GS_E_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  int gx, gy;
+  tile_grid(v, gx, gy);
+  const size_t T = (size_t)gx * gy, N = (size_t)W * H;
+  if (sc->geom_bytes < geom_bytes((size_t)P) || sc->img_bytes < img_bytes(N, T)) return GS_E_SCRATCH;
+  GeomView gv = geom_view(sc->geom, (size_t)P);
+  ImgView iv = img_view(sc->img, N, T);
+  SortBufs bv = sort_view(sc->binning, (size_t)sc->binning_capacity);
+  gs_row_t* rows = (gs_row_t*)workspace;
+  {
+    GS_PROF(ST_BWD_MEMSET, s);
+    launch_zero_rows(rows, (size_t)P, v->tile_cull ? gv.tiles_touched : nullptr, s);
+  }
+  if (num_rendered > 0) {
+    GS_PROF(ST_RENDER_BWD, s);
+    launch_depth_bwd(iv.ranges, bv.vals[0], W, H, gx, gy, gv.splat, iv.final_T, iv.n_contrib, iv.tile_work, iv.tile_order,
+                     dL_ddepth, dL_dalpha, rows, grad_flags, s);
+  }
+  GS_LAUNCH_CHECK(s, v->debug);
+  DepthPointArgs a;
+  a.P = P;
+  a.means3D = g->means3D;
+  a.radii = radii;
+  a.scales = g->scales;
+  a.rotations = g->rotations;
+  a.scale_modifier = v->scale_modifier;
+  a.cov3D = g->cov3D_precomp;
+  a.viewmatrix = v->viewmatrix;
+  a.projmatrix = v->projmatrix;
+  a.focal_y = v->image_height / (2.0f * v->tanfovy);
+  a.focal_x = v->image_width / (2.0f * v->tanfovx);
+  a.tan_fovx = v->tanfovx;
+  a.tan_fovy = v->tanfovy;
+  a.skip_uninstanced = v->tile_cull ? 1 : 0;  // (as gs_backward: only the rows of Gaussians with instances were cleared)
+  a.tiles_touched = gv.tiles_touched;
+  a.grad_rows = rows;
+  a.dL_dmeans3D = dL_dmeans3D;
+  a.dL_dmeans2D = dL_dmeans2D;
+  a.dL_dopacity = dL_dopacity;
+  {
+    GS_PROF(ST_PREPROCESS_BWD, s);
+    launch_depth_point_bwd(a, grad_flags, s);
+  }
+  GS_LAUNCH_CHECK(s, v->debug);
+  return GS_OK;
+}
+
 int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* /*projmatrix*/,
                     uint8_t* present, void* stream) {
   if (P < 0) return GS_E_SHAPE;

@@ -340,6 +340,34 @@ int launch_render_bwd_wave(const uint2* ranges, const uint32_t* point_list, int 
                            const uint32_t* tile_work, const uint32_t* tile_order, const float* dL_dpix,
                            const float* dL_dinvdepth, const float* dL_dextra, gs_row_t* grad_rows, int fsgs, hipStream_t s);
 
+// ---- the depth-only pass (gs_depth_pass.hip): depth and alpha images, gradients to the means and / or the opacities ----
+int launch_depth_fwd(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y, const Splat* splat,
+                     float* final_T, uint32_t* n_contrib, uint32_t* tile_work, float* stop_depth, float* out_depth,
+                     float* out_alpha, int cull, hipStream_t s);
+// grad_flags: 1 = sums for the means, 2 = for the opacities, 3 = both (gs_depth_backward); null cotangent = zero image
+int launch_depth_bwd(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y, const Splat* splat,
+                     const float* final_T, const uint32_t* n_contrib, const uint32_t* tile_work, const uint32_t* tile_order,
+                     const float* dL_ddepth, const float* dL_dalpha, gs_row_t* grad_rows, int grad_flags, hipStream_t s);
+struct DepthPointArgs {
+  int P;
+  const float* means3D;
+  const int* radii;
+  const float* scales;     // with rotations, or NULL: then cov3D
+  const float* rotations;
+  float scale_modifier;
+  const float* cov3D;      // the caller's precomputed covariance
+  const float* viewmatrix;
+  const float* projmatrix;
+  float focal_x, focal_y, tan_fovx, tan_fovy;
+  int skip_uninstanced;    // as PreprocessBwdArgs.skip_uninstanced
+  const uint32_t* tiles_touched;
+  const gs_row_t* grad_rows;
+  float* dL_dmeans3D;      // [P,3]  (grad_flags & 1)
+  float* dL_dmeans2D;      // [P,3]  (grad_flags & 1)
+  float* dL_dopacity;      // [P]    (grad_flags & 2)
+};
+int launch_depth_point_bwd(const DepthPointArgs& a, int grad_flags, hipStream_t s);
+
 int launch_blend_stats(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y, const Splat* splat,
                        const uint32_t* n_contrib, const uint32_t* tile_work, unsigned long long* out, hipStream_t s);
 

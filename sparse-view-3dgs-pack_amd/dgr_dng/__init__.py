@@ -56,3 +56,51 @@ class GaussianRasterizationSettings(NamedTuple):
 
 class GaussianRasterizer(dgr_fsgs.GaussianRasterizer):
     _fn = _RasterizeGaussians
+
+
+# ---- DNGaussian's two depth passes, served by the depth-only kernels (gsplat_amd.depth_pass) ------------------------------
+def _depth_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
+    import math
+    return GaussianRasterizationSettings(
+        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
+        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
+        campos=viewpoint_camera.camera_center, prefiltered=False, debug=pipe.debug)
+
+
+def _depth_shape(pc, pipe, scaling_modifier):
+    """-> (scales, rotations, cov3D_precomp), detached.  (The reference's render_for_opa leaves a Python-side covariance
+    attached; this pass produces no gradient for it.)"""
+    if pipe.compute_cov3D_python:
+        return None, None, pc.get_covariance(scaling_modifier).detach()
+    return pc.get_scaling.detach(), pc.get_rotation.detach(), None
+
+
+def render_for_depth(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, value=0.95):
+    """DNGaussian's "hard depth" pass (gaussian_renderer/__init__.py:128-197): every opacity is `value`, the loss reaches the
+    means only.  Same arguments and returned keys as the reference's function, except that there is no "render" (a colour
+    image of ones that neither training script reads)."""
+    from gsplat_amd.depth_pass import depth_pass
+    xyz = pc.get_xyz
+    screenspace_points = torch.zeros_like(xyz, requires_grad=True)
+    scales, rotations, cov = _depth_shape(pc, pipe, scaling_modifier)
+    depth, alpha, radii = depth_pass(_depth_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier), xyz, float(value),
+                                     scales, rotations, cov, grad="means", means2D=screenspace_points)
+    return {"depth": depth, "alpha": alpha, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+            "radii": radii}
+
+
+def render_for_opa(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
+    """DNGaussian's "soft depth" pass (gaussian_renderer/__init__.py:201-269): the model's opacities, the loss reaches them
+    only.  Same arguments and returned keys as the reference's function, without "render"; `viewspace_points` receives no
+    gradient in this pass (the means are detached there too)."""
+    from gsplat_amd.depth_pass import depth_pass
+    xyz = pc.get_xyz
+    screenspace_points = torch.zeros_like(xyz, requires_grad=True)
+    opacity = pc.get_opacity
+    scales, rotations, cov = _depth_shape(pc, pipe, scaling_modifier)
+    depth, alpha, radii = depth_pass(_depth_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier), xyz.detach(),
+                                     opacity, scales, rotations, cov, grad="opacity")
+    return {"depth": depth, "alpha": alpha, "viewspace_points": screenspace_points, "visibility_filter": radii > 0,
+            "radii": radii, "opacity": opacity}

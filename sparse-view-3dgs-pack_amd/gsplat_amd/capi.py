@@ -135,6 +135,9 @@ PROTOTYPES = {
     "forward_render_fsgs": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P, _P, _P]),
     "backward_fsgs": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, _P,
                                 C.POINTER(GsGrads), _P, _SZ, _P]),
+    "depth_forward": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P, _P]),
+    "depth_backward": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, C.c_int,
+                                 _P, _P, _P, _P, _SZ, _P]),
     "step_uninstanced": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch),
                                    C.POINTER(GsStepState), _P]),
     "backward_step": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P,
@@ -270,7 +273,10 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # (tests/densify_reference.py restates the plan in torch)
                "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather",
                # test-set evaluation (PSNR / SSIM / L1 per view): restated in torch (tests/eval_reference.py)
-               "eval_partials_count", "eval_tmp_bytes", "eval_metrics")
+               "eval_partials_count", "eval_tmp_bytes", "eval_metrics",
+               # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
+               # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
+               "depth_forward", "depth_backward")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

@@ -14,6 +14,7 @@ import torch
 from .capi import GsGaussians, GsGrads, GsScratch, GsView
 
 NUM_CHANNELS = 3
+_DEPTH_ONLY = 2   # _Forward.fsgs of a depth-only forward (RasterBackend.depth_forward): _render calls gs_depth_forward
 
 
 def _ptr(t):
@@ -825,7 +826,10 @@ class RasterBackend:
         if f.use_limit:
             scratch.tile_depth_limit_out = c["limit"].data_ptr()
             scratch.tile_depth_limit_slack = c["slack"].data_ptr()
-        if f.fsgs:
+        if f.fsgs == _DEPTH_ONLY:
+            self.api.call("depth_forward", C.byref(f.view), C.byref(f.g), C.byref(scratch), f.out_invdepth.data_ptr(),
+                          f.out_extra.data_ptr(), f.stream)
+        elif f.fsgs:
             self.api.call("forward_render_fsgs", C.byref(f.view), C.byref(f.g), C.byref(scratch), f.out_color.data_ptr(),
                           f.out_invdepth.data_ptr(), f.out_extra.data_ptr(), f.stream)
         elif f.extra is None:
@@ -855,6 +859,74 @@ class RasterBackend:
         done, self._tile_order_done = getattr(self, "_tile_order_done", None), None
         if done is not None:
             torch.cuda.current_stream(device).wait_event(done)
+
+    # ------------------------------------------------------------------ the depth-only pass
+    def depth_forward(self, means3D, opacities, scales, rotations, cov3D_precomp, scale_modifier, bg, viewmatrix, projmatrix,
+                      campos, tanfovx, tanfovy, image_height, image_width, debug=False):
+        """gs_depth_forward behind the forward sequence of rasterize_gaussians(fsgs=True): geometry, its one read-back of
+        num_rendered, the binning allocation, the backend's kind of lists (tile_cull / binning).  No colour image.
+        -> (depth [1,H,W], alpha [1,H,W], radii [P] int32, record for depth_backward or None when P == 0)
+
+        The pass owns its scratch: it neither reads nor writes the last-forward record, the per-camera hints and depth
+        limits, the one-shot requests (grad_arena, fused_step, raw_activations, ...) of the general path.  It shares the
+        binning capacity hint, which only sizes buffers."""
+        if means3D.ndim != 2 or means3D.shape[1] != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, 3)")
+        self._check_device(means3D)
+        device = means3D.device
+        P, H, W = int(means3D.shape[0]), int(image_height), int(image_width)
+        f32 = dict(dtype=torch.float32, device=device)
+        alloc = torch.empty if P != 0 else torch.zeros
+        depth, alpha = alloc((1, H, W), **f32), alloc((1, H, W), **f32)
+        radii = alloc((P,), dtype=torch.int32, device=device)
+        if P == 0:
+            return depth, alpha, radii, None
+        tile_cull = self._tile_cull(device)
+        if tile_cull == 2 and ((P, W, H, False) in self._region_off or (
+                self.binning == "auto" and self._capacity_hint > self.REGION_AUTO_MAX * _regions(W, H))):
+            tile_cull = 1
+        keep = []
+        view = self._view(keep, device, bg, viewmatrix, projmatrix, campos, tanfovx, tanfovy, H, W, scale_modifier, 0, False,
+                          False, debug, tile_cull=tile_cull)
+        # the geometry phase wants a colour source; this pass never reads the colours it leaves in the records, so any
+        # [P,3] array serves: the means themselves (no tensor of ones is built)
+        g = self._gauss(keep, device, means3D, None, means3D, opacities, scales, rotations, cov3D_precomp)
+        gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
+        u8 = dict(dtype=torch.uint8, device=device)
+        geom, img = torch.empty((gb,), **u8), torch.empty((ib,), **u8)
+        if self.scratch_fill is not None:
+            self.scratch_fill("geom", geom)
+            self.scratch_fill("img", img)
+        f = _Forward(device, self._stream(device), view, g, P, W, H, geom, img, radii, None, depth, alpha, _DEPTH_ONLY, None,
+                     None, False, False, False)
+        f.cur = torch.cuda.current_stream(device)
+        pkey = (device.index, f.cur.cuda_stream)
+        status = self._pinned_by_device.get(pkey)
+        if status is None:
+            status = self._pinned_by_device[pkey] = torch.zeros((16,), dtype=torch.int32).pin_memory()
+        f.status = status
+        num_rendered, binning = self._forward_lists(f, None, False)
+        return depth, alpha, radii, dict(view=f.view, g=g, keep=keep, radii=radii, geom=geom, img=img, binning=binning,
+                                         R=int(num_rendered), P=P, W=W, H=H)
+
+    def depth_backward(self, rec, dL_ddepth, dL_dalpha, grad_flags):
+        """gs_depth_backward on the record of a depth_forward.  grad_flags: 1 means, 2 opacities, 3 both; a cotangent may be
+        None (zero).  -> (dL_dmeans3D [P,3], dL_dmeans2D [P,3], dL_dopacity [P,1]), None for what was not asked for."""
+        device = rec["radii"].device
+        P, W, H, R = rec["P"], rec["W"], rec["H"], rec["R"]
+        f32 = dict(dtype=torch.float32, device=device)
+        dL_ddepth, dL_dalpha = _prep(dL_ddepth, device), _prep(dL_dalpha, device)
+        # every row of a requested output is written by the per-Gaussian kernel (zeros for culled rows): empty, not zeros
+        dm3 = torch.empty((P, 3), **f32) if grad_flags & 1 else None
+        dm2 = torch.empty((P, 3), **f32) if grad_flags & 1 else None
+        dop = torch.empty((P, 1), **f32) if grad_flags & 2 else None
+        ws = torch.empty((((P * 128 + 255) // 256) * 256,), dtype=torch.uint8, device=device)
+        binning = rec["binning"]
+        s = self._scratch(rec["geom"], rec["img"], binning, self._capacity_for(binning, P, W, H, R))
+        self.api.call("depth_backward", C.byref(rec["view"]), C.byref(rec["g"]), rec["radii"].data_ptr(), C.byref(s), R,
+                      _ptr(dL_ddepth), _ptr(dL_dalpha), int(grad_flags), _ptr(dm3), _ptr(dm2), _ptr(dop), ws.data_ptr(),
+                      ws.numel(), self._stream(device))
+        return dm3, dm2, dop
 
     # ------------------------------------------------------------------ backward
     def rasterize_gaussians_backward(self, bg, means3D, radii, colors_precomp, opacities, scales, rotations,
