@@ -253,6 +253,20 @@ int gs_backward_x(const GsView* view, const GsGaussians* g, const int32_t* radii
                   const float* dL_dinvdepth, const float* dL_dextra_img, const GsGrads* grads,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* gs_backward for the model's SPLIT SH rows (GsGaussians.shs_rest != NULL, raw_activations == 0): what the reference's
+ * `rasterizer(dc=pc.get_features_dc, shs=pc.get_features_rest, ...)` call needs (gaussian_renderer/__init__.py:82-100).
+ * grads->dL_dsh is then the gradient of the DC rows, [P,1,3], and dL_dsh_rest that of g->shs_rest, [P,M-1,3]: one
+ * contiguous gradient per model tensor, both FULLY written (zeros for culled Gaussians and for the coefficients above the
+ * active degree: allocate them uninitialised), straight from the per-Gaussian kernel - no [P,M,3] intermediate, no copy.
+ * Values are bit for bit the slices [:, :1] and [:, 1:] of the dL_dsh that gs_backward writes for the concatenated rows.
+ * Everything else - the other gradients, anti-aliasing, dL_dinvdepth, the workspace - is gs_backward.
+ * GS_E_UNSUPPORTED: g->shs_rest == NULL or raw_activations set; GS_E_NULL: dL_dsh_rest or grads->dL_dsh missing; no launch
+ * in either case.  (gs_backward itself keeps answering GS_E_UNSUPPORTED for split rows.) */
+int gs_backward_split(const GsView* view, const GsGaussians* g, const int32_t* radii,
+                      const GsScratch* scratch, int64_t num_rendered, const float* dL_dcolor,
+                      const float* dL_dinvdepth, const GsGrads* grads, float* dL_dsh_rest, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* The older rasterizer generation used by FSGS / DNGaussian (SURVEY 8f-4;
  * FSGS/submodules/diff-gaussian-rasterization-confidence: `rasterize_gaussians` returns colour, depth, alpha -
  * rasterize_points.cu, forward.cu:262-380; backward takes their three image gradients, backward.cu:414-600).
@@ -865,6 +879,43 @@ int gs_adam_step_gated(float* params, const float* grads, float* exp_avg, float*
 int gs_adam_step_masked(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                         const GsAdamSeg* segs, int32_t nseg, float beta1, float beta2, float eps, int32_t step,
                         const float* gate, const float* row_mask, void* stream);
+
+/* The optimizer behind the reference's OWN API: the parameter tensors of up to 8 param groups (gaussian_model.py:183-193:
+ * six groups, one tensor each, sizes P * {3,3,45,1,3,4}) stepped by ONE launch, each with its own learning rate and step
+ * count.  `t` is a HOST array (copied into the launch).  Tensors with n == 0 are skipped; nt == 0 returns GS_OK without a
+ * launch.
+ * row_mask (device, [P] bytes - torch.bool's storage, 0 = not stepped - or NULL = every row): a tensor with row_width > 0 is
+ * stepped only in the rows r with row_mask[r] != 0 (element i belongs to row i / row_width); every other row keeps every
+ * bit of param, exp_avg and exp_avg_sq (NaNs included) and grad is only read.  The kernel reads the mask bytes of a float4's
+ * rows first: a float4 without a stepped element is neither loaded nor stored, so the traffic is P mask bytes + 28 B times the
+ * elements of the float4s that hold a stepped element.
+ * Two rules, each ONE expression order (csrc/gs_adam.hip is compiled without contraction):
+ *   flags == 0: the arithmetic of the gs_adam_step family to the letter,
+ *       m = b1*m + (1-b1)*g;  v = b2*v + ((1-b2)*g)*g;  p = p - (lr * inv_bc1) * (m / (sqrtf(v) * inv_sqrt_bc2 + eps))
+ *     with inv_bc1 = (float)(1 / (1 - b1^step)), inv_sqrt_bc2 = (float)(1 / sqrt(1 - b2^step)) formed in double: on one
+ *     tensor with every row stepped the bits are gs_adam_step's, with a mask they are gs_adam_step_masked's.
+ *   GS_ADAM_NO_BIAS_CORRECTION: the rule of the accelerated rasterizer's SparseGaussianAdam,
+ *       m = b1*m + (1-b1)*g;  v = b2*v + ((1-b2)*g)*g;  p = p - lr * (m / (sqrtf(v) + eps))
+ *     (`step` is not read).  That optimizer's source is NOT in the reference tree (train.py only probes for the class): the
+ *     rule - Adam's moments, no bias correction - is known here only from this project's review notes, and the
+ *     association lr * (m / denom) is this project's choice (the same as in the rule above), not a transcription.
+ * GS_E_NULL: t missing, or a null pointer in a tensor with n > 0; GS_E_SHAPE: nt outside 0..8, n < 0, row_width < 0,
+ * step < 1 with flags == 0, or a mask given while a tensor has row_width > 0 and n != P * row_width; GS_E_UNSUPPORTED: a
+ * tensor base that is not 16-byte aligned (as gs_adam_step), or an unknown flag bit. */
+typedef struct GsAdamTensor { /* one parameter tensor of a group */
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;         /* elements */
+  int32_t row_width; /* floats per Gaussian (n == P * row_width) when row_mask is given; 0 = this tensor is never masked */
+  int32_t step;      /* 1-based step count of THIS tensor for the bias correction */
+  float lr;
+  int32_t pad;
+} GsAdamTensor;
+#define GS_ADAM_NO_BIAS_CORRECTION 1
+int gs_adam_step_tensors(const GsAdamTensor* t, int32_t nt, int64_t P, float beta1, float beta2, float eps, int32_t flags,
+                         const uint8_t* row_mask, void* stream);
 
 /* ---- per-Gaussian elementwise work of the train step outside the rasterizer ----
  * Parameter activations of GaussianModel (LGDWT-GS/scene/gaussian_model.py:40-60,102-117): scales = exp(scaling),

@@ -324,7 +324,17 @@ int gs_backward(const GsView* v, const GsGaussians* g, const int32_t* radii, con
 static int backward_impl(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc,
                          int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, const float* dL_dextra,
                          int fsgs, const GsGrads* grads, void* workspace, size_t workspace_bytes, void* stream,
-                         const GsStepState* step = nullptr);
+                         const GsStepState* step = nullptr, float* dsh_rest_out = nullptr);
+
+int gs_backward_split(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc,
+                      int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, const GsGrads* grads,
+                      float* dL_dsh_rest, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!g || !grads) return GS_E_NULL;
+  if (!g->shs_rest || g->raw_activations) return GS_E_UNSUPPORTED;  // (one [P,M,3] row array: gs_backward)
+  if (!dL_dsh_rest || !grads->dL_dsh) return GS_E_NULL;
+  return backward_impl(v, g, radii, sc, num_rendered, dL_dcolor, dL_dinvdepth, nullptr, 0, grads, workspace, workspace_bytes,
+                       stream, nullptr, dL_dsh_rest);
+}
 
 int gs_backward_x(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc,
                   int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, const float* dL_dextra,
@@ -433,12 +443,12 @@ static int step_args(const GsGaussians* g, const GsStepState* st, StepArgs& sa) 
 static int backward_impl(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc,
                          int64_t num_rendered, const float* dL_dcolor, const float* dL_dinvdepth, const float* dL_dextra,
                          int fsgs, const GsGrads* grads, void* workspace, size_t workspace_bytes, void* stream,
-                         const GsStepState* step) {
+                         const GsStepState* step, float* dsh_rest_out) {
   int rc = check_args(v, g);
   if (rc) return rc;
   if (!sc || !grads || !dL_dcolor) return GS_E_NULL;
   if (g->raw_activations && !step) return GS_E_UNSUPPORTED;  // gradients w.r.t. activated values that were never formed
-  if (g->shs_rest && !step) return GS_E_UNSUPPORTED;         // GsGrads.dL_dsh is one [P,M,3] array
+  if (g->shs_rest && !step && !dsh_rest_out) return GS_E_UNSUPPORTED;  // GsGrads.dL_dsh is one [P,M,3] array (gs_backward_split)
   StepArgs sa;
   if (step && g->P > 0) {
     rc = step_args(g, step, sa);
@@ -513,7 +523,7 @@ static int backward_impl(const GsView* v, const GsGaussians* g, const int32_t* r
     launch_preprocess_bwd_step(a, sa, s);
   } else {
     GS_PROF(ST_PREPROCESS_BWD, s);
-    launch_preprocess_bwd(a, s);
+    launch_preprocess_bwd(a, s, dsh_rest_out);
   }
   GS_LAUNCH_CHECK(s, v->debug);
   return GS_OK;

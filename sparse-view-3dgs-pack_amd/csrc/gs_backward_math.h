@@ -20,6 +20,7 @@ struct ShRegsB {
 struct ShSink {
   float* p;
   bool basis_only;
+  float* rest = nullptr;  // generic M, split rows (gs_backward_split): row 0 goes to p, row k > 0 to rest + 3 (k - 1)
   __host__ __device__ __forceinline__ void rgb(V3 g) const {
     if (basis_only) {
       p[16] = g.x;
@@ -31,9 +32,10 @@ struct ShSink {
     if (basis_only) {
       p[k] = basis;
     } else {
-      p[3 * k] = basis * g.x;
-      p[3 * k + 1] = basis * g.y;
-      p[3 * k + 2] = basis * g.z;
+      float* q = (rest && k > 0) ? rest + 3 * (k - 1) : p + 3 * k;
+      q[0] = basis * g.x;
+      q[1] = basis * g.y;
+      q[2] = basis * g.z;
     }
   }
 };

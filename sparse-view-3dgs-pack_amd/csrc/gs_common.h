@@ -422,7 +422,8 @@ static inline __device__ bool gs_instanced(const PreprocessBwdArgs& a, bool use_
   return use_reached ? a.reached[idx] != 0 : a.tiles_touched[idx] != 0u;
 }
 int launch_chain(const PreprocessBwdArgs& a, const GeomHeader* hdr, hipStream_t s);
-int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s);
+// dsh_rest_out (gs_backward_split): a.out.dL_dsh is then the DC rows' gradient [P,1,3], dsh_rest_out the rest rows' [P,M-1,3]
+int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, float* dsh_rest_out = nullptr);
 // the same stage with the train step's tail fused in (gs_backward_step); bias corrections precomputed on the host
 struct StepArgs {
   GsStepState st;

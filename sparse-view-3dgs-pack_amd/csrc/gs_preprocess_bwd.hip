@@ -92,7 +92,42 @@ int launch_chain(const PreprocessBwdArgs& a, const GeomHeader* hdr, hipStream_t 
   return 0;
 }
 
-__global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_kernel(PreprocessBwdArgs a) {
+// the workgroup's piece of one gradient row array written out: `cnt` Gaussians x N floats starting at element first * N, float4
+// stores when the piece starts on 16 bytes (the data-parallel step's gradients; gs_backward_split's two SH pieces)
+template <int N, typename G>
+__device__ __forceinline__ void grad_block(float* __restrict__ out, int first, int cnt, const G& grad) {
+  float* of = out + (size_t)first * N;
+  const int nfl = cnt * N;
+  if ((((uintptr_t)of) & 15) == 0 && (nfl % 4 == 0)) {
+    for (int j = 4 * threadIdx.x; j < nfl; j += 4 * GS_BLOCK)
+      *reinterpret_cast<float4*>(of + j) = make_float4(grad(j), grad(j + 1), grad(j + 2), grad(j + 3));
+  } else {
+    for (int j = threadIdx.x; j < nfl; j += GS_BLOCK) of[j] = grad(j);
+  }
+}
+// split rows (M == 16): one contiguous gradient per model tensor (_features_dc [P,1,3], _features_rest [P,15,3]) from the
+// workgroup's 19-word LDS rows - dL_dsh[r][k][ch] = basis_k * dL_dRGB[ch]
+struct ShGradDc {
+  const float* s;
+  __device__ __forceinline__ float operator()(int j) const {
+    const int r = j / 3, ch = j - 3 * r;
+    const float* src = s + r * SH_LDS_ROW;
+    return src[0] * src[16 + ch];
+  }
+};
+struct ShGradRest {
+  const float* s;
+  __device__ __forceinline__ float operator()(int j) const {
+    const int r = j / 45, c = j - r * 45, k = c / 3, ch = c - 3 * k;
+    const float* src = s + r * SH_LDS_ROW;
+    return src[k + 1] * src[16 + ch];
+  }
+};
+
+// SPLIT (gs_backward_split; dsh_rest_out: the rest rows' gradient [P,M-1,3], a.out.dL_dsh the DC rows' [P,1,3]): its own
+// instantiation, so that gs_backward's kernel is unchanged
+template <bool SPLIT>
+__global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_kernel(PreprocessBwdArgs a, float* dsh_rest_out) {
   // dL_dsh rows (192 B per Gaussian) leave through LDS so that every store instruction of a wave covers 1 KiB of
   // consecutive addresses; written per lane (12 x 16 B at a 192-B stride) the same bytes cost 2.3x the HBM write
   // traffic (rocprofv3 WRITE_SIZE, profiles/).  Row stride 19 words (odd): conflict-free per-lane writes.
@@ -106,10 +141,15 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_kernel(PreprocessB
   // dL_dsh sink: zero row first (culled Gaussians and coefficients above the active degree stay 0)
   const bool sh_lds = a.shs && a.out.dL_dsh && a.M == 16;
   const bool sh_global = a.shs && a.out.dL_dsh && !sh_lds && in_range;  // generic M: straight to the global row
-  ShSink dsh{sh_global ? a.out.dL_dsh + (size_t)idx * a.M * 3 : s_sh + threadIdx.x * SH_LDS_ROW, !sh_global};
+  // gs_backward_split: the DC row's gradient goes to out.dL_dsh [P,1,3], rows 1..M-1 to dsh_rest_out [P,M-1,3]
+  float* const rest_row = (SPLIT && sh_global) ? dsh_rest_out + (size_t)idx * (a.M - 1) * 3 : nullptr;
+  ShSink dsh{sh_global ? a.out.dL_dsh + (size_t)idx * (SPLIT ? 1 : a.M) * 3 : s_sh + threadIdx.x * SH_LDS_ROW, !sh_global,
+             rest_row};
   {
-    const int nfl_row = sh_global ? a.M * 3 : SH_LDS_ROW;
+    const int nfl_row = sh_global ? (SPLIT ? 3 : a.M * 3) : SH_LDS_ROW;
     for (int k = 0; k < nfl_row; k++) dsh.p[k] = 0.f;
+    if (SPLIT && rest_row)
+      for (int k = 0; k < (a.M - 1) * 3; k++) rest_row[k] = 0.f;
   }
 
   const bool active = visible && !(a.skip_uninstanced && a.tiles_touched[idx] == 0);  // see PreprocessBwdArgs
@@ -153,7 +193,13 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_kernel(PreprocessB
     o.dL_dmeans3D[3 * idx + 1] = gb.dmean.y;
     o.dL_dmeans3D[3 * idx + 2] = gb.dmean.z;
   }
-  if (sh_lds) {
+  if (SPLIT && sh_lds) {  // split rows: two coalesced pieces per workgroup, 3 and 45 floats per Gaussian
+    __syncthreads();
+    const int first = blockIdx.x * GS_BLOCK;
+    const int cnt = min(GS_BLOCK, a.P - first);
+    grad_block<3>(o.dL_dsh, first, cnt, ShGradDc{s_sh});
+    grad_block<45>(dsh_rest_out, first, cnt, ShGradRest{s_sh});
+  } else if (sh_lds) {
     __syncthreads();
     const int first = blockIdx.x * GS_BLOCK;
     const int nfl = min(GS_BLOCK, a.P - first) * 48;  // floats this workgroup owns, a multiple of 4
@@ -172,8 +218,10 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_kernel(PreprocessB
   }
 }
 
-int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(preprocess_bwd_kernel, dim3((a.P + GS_BLOCK - 1) / GS_BLOCK), dim3(GS_BLOCK), 0, s, a);
+int launch_preprocess_bwd(const PreprocessBwdArgs& a, hipStream_t s, float* dsh_rest_out) {
+  const dim3 grid((a.P + GS_BLOCK - 1) / GS_BLOCK), block(GS_BLOCK);
+  if (dsh_rest_out) hipLaunchKernelGGL(preprocess_bwd_kernel<true>, grid, block, 0, s, a, dsh_rest_out);
+  else hipLaunchKernelGGL(preprocess_bwd_kernel<false>, grid, block, 0, s, a, (float*)nullptr);
   return 0;
 }
 
@@ -292,19 +340,6 @@ __device__ __forceinline__ void adam_block(float* __restrict__ p, float* __restr
       mf[j] = me;
       vf[j] = ve;
     }
-  }
-}
-
-// data-parallel form: the workgroup's piece of one gradient row array written out (same element order as adam_block reads)
-template <int N, typename G>
-__device__ __forceinline__ void grad_block(float* __restrict__ out, int first, int cnt, const G& grad) {
-  float* of = out + (size_t)first * N;
-  const int nfl = cnt * N;
-  if ((((uintptr_t)of) & 15) == 0 && (nfl % 4 == 0)) {
-    for (int j = 4 * threadIdx.x; j < nfl; j += 4 * GS_BLOCK)
-      *reinterpret_cast<float4*>(of + j) = make_float4(grad(j), grad(j + 1), grad(j + 2), grad(j + 3));
-  } else {
-    for (int j = threadIdx.x; j < nfl; j += GS_BLOCK) of[j] = grad(j);
   }
 }
 
@@ -526,22 +561,6 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_step_kernel(Prepro
       grad_block<3>(st.grad_out[3], first, cnt, Lds{s_g + SG_SCALE});
       grad_block<4>(st.grad_out[4], first, cnt, Lds{s_g + SG_ROT});
       if (st.grad_out_rest) {  // split rows: one contiguous gradient per model tensor (_features_dc, _features_rest)
-        struct ShGradDc {
-          const float* s;
-          __device__ __forceinline__ float operator()(int j) const {
-            const int r = j / 3, ch = j - 3 * r;
-            const float* src = s + r * SH_LDS_ROW;
-            return src[0] * src[16 + ch];
-          }
-        };
-        struct ShGradRest {
-          const float* s;
-          __device__ __forceinline__ float operator()(int j) const {
-            const int r = j / 45, c = j - r * 45, k = c / 3, ch = c - 3 * k;
-            const float* src = s + r * SH_LDS_ROW;
-            return src[k + 1] * src[16 + ch];
-          }
-        };
         grad_block<3>(st.grad_out[1], first, cnt, ShGradDc{s_sh});
         grad_block<45>(st.grad_out_rest, first, cnt, ShGradRest{s_sh});
       } else {

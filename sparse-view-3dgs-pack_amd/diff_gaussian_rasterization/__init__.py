@@ -6,8 +6,11 @@ Public surface (same names, argument order, defaults, return values and error be
   GaussianRasterizationSettings   NamedTuple, 13 fields        dgr_3dgs/__init__.py:143-156
   GaussianRasterizer(nn.Module)   forward / markVisible         dgr_3dgs/__init__.py:158-207
   rasterize_gaussians, _RasterizeGaussians                      dgr_3dgs/__init__.py:21-141
-`SparseGaussianAdam` is intentionally absent (LGDWT-GS/train.py:42-46 probes for it and would
-switch the renderer to an API this rasterizer generation does not have).
+`SparseGaussianAdam` is absent from THIS package on purpose: LGDWT-GS/train.py:42-46 probes for it and, finding it,
+switches the optimizer and the renderer (`rasterizer(dc=..., shs=...)`) by itself - a maintainer opts into that.  The
+opt-in is one more PYTHONPATH entry: sparse-view-3dgs-pack_amd/accel in front of this directory's parent puts a package
+of the same name first that exports everything below, the class, and a GaussianRasterizer whose forward() takes `dc=`
+(gsplat_amd.accel, gsplat_amd.optim).
 """
 from typing import NamedTuple
 

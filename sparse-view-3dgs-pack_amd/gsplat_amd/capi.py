@@ -95,6 +95,15 @@ class GsAdamSeg(C.Structure):
                 ("period", C.c_int32), ("split", C.c_int32), ("step", C.c_int32), ("row_width", C.c_int32)]
 
 
+class GsAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("n", C.c_int64), ("row_width", C.c_int32), ("step", C.c_int32), ("lr", C.c_float), ("pad", C.c_int32)]
+
+
+ADAM_NO_BIAS_CORRECTION = 1   # GS_ADAM_NO_BIAS_CORRECTION
+ADAM_MAX_TENSORS = 8          # tensors per gs_adam_step_tensors call
+
+
 class GsStepState(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("features", C.c_void_p), ("opacity", C.c_void_p), ("scaling", C.c_void_p),
                 ("rotation", C.c_void_p), ("m", C.c_void_p * 5), ("v", C.c_void_p * 5), ("lr", C.c_float * 6),
@@ -130,6 +139,8 @@ PROTOTYPES = {
     "backward": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P,
                            C.POINTER(GsGrads), _P, _SZ, _P]),
     "forward_render_x": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P, _P, _P]),
+    "backward_split": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P,
+                                 C.POINTER(GsGrads), _P, _P, _SZ, _P]),
     "backward_x": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, _P,
                              C.POINTER(GsGrads), _P, _SZ, _P]),
     "forward_render_fsgs": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P, _P, _P]),
@@ -223,6 +234,7 @@ PROTOTYPES = {
     "adam_step": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P]),
     "adam_step_gated": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P, _P]),
     "adam_step_masked": (C.c_int, [_P, _P, _P, _P, _I64, C.POINTER(GsAdamSeg), _I32, _F, _F, _F, _I32, _P, _P, _P]),
+    "adam_step_tensors": (C.c_int, [C.POINTER(GsAdamTensor), _I32, _I64, _F, _F, _F, _I32, _P, _P]),
     "activations_fwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P]),
     "activations_bwd": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "densify_stats": (C.c_int, [_P, _P, _I32, _P, _P, _P, _P]),
@@ -276,7 +288,10 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                "eval_partials_count", "eval_tmp_bytes", "eval_metrics",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
-               "depth_forward", "depth_backward")
+               "depth_forward", "depth_backward",
+               # the reference-API optimizer's one-launch step (restated in numpy: tests/sparse_adam_reference.py) and the backward
+               # for the model's split SH rows - a memory layout of the product, compared against gs_backward's slices on the GPU
+               "adam_step_tensors", "backward_split")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

@@ -54,9 +54,14 @@ class DropInModel:
         self.denom[update_filter] += 1
 
 
-def render(cam, pc, bg_color, camera_key=None):
-    """gaussian_renderer/__init__.py:18-128 (SH evaluated by the rasterizer, scales + rotations given, no exposure)."""
-    from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+def render(cam, pc, bg_color, camera_key=None, separate_sh=False):
+    """gaussian_renderer/__init__.py:18-128 (SH evaluated by the rasterizer, scales + rotations given, no exposure).
+    separate_sh: the call of :82-100, `rasterizer(dc=pc._features_dc, shs=pc._features_rest, ...)`, through the opt-in
+    rasterizer class (gsplat_amd.accel) - no torch.cat, one gradient per tensor."""
+    if separate_sh:
+        from .accel import GaussianRasterizationSettings, GaussianRasterizer
+    else:
+        from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
     screenspace_points = torch.zeros_like(pc._xyz, dtype=pc._xyz.dtype, requires_grad=True, device=pc._xyz.device) + 0
     screenspace_points.retain_grad()
     settings = GaussianRasterizationSettings(
@@ -67,10 +72,16 @@ def render(cam, pc, bg_color, camera_key=None):
     rasterizer = GaussianRasterizer(raster_settings=settings)
     if camera_key is not None:          # the one optional addition: who this camera is
         rasterizer.camera_key = camera_key
-    shs = torch.cat((pc._features_dc, pc._features_rest), dim=1)
-    rendered_image, radii, depth_image = rasterizer(
-        means3D=pc._xyz, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=torch.sigmoid(pc._opacity),
-        scales=torch.exp(pc._scaling), rotations=torch.nn.functional.normalize(pc._rotation), cov3D_precomp=None)
+    if separate_sh:
+        rendered_image, radii, depth_image = rasterizer(
+            means3D=pc._xyz, means2D=screenspace_points, dc=pc._features_dc, shs=pc._features_rest, colors_precomp=None,
+            opacities=torch.sigmoid(pc._opacity), scales=torch.exp(pc._scaling),
+            rotations=torch.nn.functional.normalize(pc._rotation), cov3D_precomp=None)
+    else:
+        shs = torch.cat((pc._features_dc, pc._features_rest), dim=1)
+        rendered_image, radii, depth_image = rasterizer(
+            means3D=pc._xyz, means2D=screenspace_points, shs=shs, colors_precomp=None, opacities=torch.sigmoid(pc._opacity),
+            scales=torch.exp(pc._scaling), rotations=torch.nn.functional.normalize(pc._rotation), cov3D_precomp=None)
     rendered_image = rendered_image.clamp(0, 1)
     return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": (radii > 0).nonzero(),
             "radii": radii, "depth": depth_image}
@@ -90,7 +101,7 @@ class DropInLoop:
     """One object = one training run's state (model, optimizer, the running mean of train.py:75)."""
 
     def __init__(self, scene, cameras, gt_images, device, dwt=True, patch=True, optimizer="torch", use_camera_key=False,
-                 fused_criterion=False, raw_render=False):
+                 fused_criterion=False, raw_render=False, separate_sh=False):
         self.pc = DropInModel(scene, device)
         self.cameras, self.gts = cameras, gt_images
         self.bg = torch.zeros(3, device=device)
@@ -102,14 +113,21 @@ class DropInLoop:
         # `from gsplat_amd.render_raw import render` instead of the reference's gaussian_renderer.render
         # (same signature and dict; the model's six raw tensors go to the library, no activation / cat kernels)
         self.raw_render = raw_render
+        # the reference's own accelerated path - render with dc= / shs= (separate_sh) and step
+        # SparseGaussianAdam on the rows the view saw (optimizer="sparse_adam": train.py:282-284)
+        self.separate_sh = separate_sh
         # INTEGRATION.md section 1, "optional, faster": the loss calls of train.py:128-202 replaced by ONE call of
         # lgdwt_loss.criterion() (same terms, the running mean kept on the device: no `.item()`), ELF masks cached per camera
         self.criterion, self.masks = None, {}
         if fused_criterion:
             import lgdwt_loss
             self.criterion = lgdwt_loss.criterion(dwt_enable=dwt, patch_dwt_enable=patch)
+        self.sparse_adam = optimizer == "sparse_adam"
         if optimizer == "torch":
             self.optimizer = torch.optim.Adam(self.pc.groups(), lr=0.0, eps=1e-15)
+        elif self.sparse_adam:
+            from .optim import SparseGaussianAdam
+            self.optimizer = SparseGaussianAdam(self.pc.groups(), lr=0.0, eps=1e-15)
         else:
             from .optim import FusedAdam
             self.optimizer = FusedAdam(self.pc.groups(), lr=0.0, eps=1e-15)
@@ -125,7 +143,7 @@ class DropInLoop:
             from .render_raw import render as render_raw
             pkg = render_raw(self.cameras[ci], pc, _PIPE, self.bg, camera_key=key)
         else:
-            pkg = render(self.cameras[ci], pc, self.bg, camera_key=key)
+            pkg = render(self.cameras[ci], pc, self.bg, camera_key=key, separate_sh=self.separate_sh)
         image, vsp, vis, radii = pkg["render"], pkg["viewspace_points"], pkg["visibility_filter"], pkg["radii"]
         gt = self.gts[ci]
         if self.criterion is not None:
@@ -171,6 +189,10 @@ class DropInLoop:
             vf = vis.squeeze(1)
             pc.max_radii2D[vf] = torch.max(pc.max_radii2D[vf], radii[vf].to(torch.float32))
             pc.add_densification_stats(vsp, vf)
-            self.optimizer.step()   # train.py:284-285
+            if self.sparse_adam:    # train.py:282-284
+                visible = radii > 0
+                self.optimizer.step(visible, radii.shape[0])
+            else:
+                self.optimizer.step()   # train.py:284-285
             self.optimizer.zero_grad(set_to_none=True)
         return value

@@ -147,6 +147,9 @@ class RasterBackend:
         # one-shot, set before a forward / a fused backward on raw rows: the model's _features_rest [P,M-1,3]; `sh` is then
         # _features_dc [P,1,3] (GsGaussians.shs_rest: the kernels read the split rows, no torch.cat)
         self.sh_rest = None
+        # one-shot, set WITH sh_rest by gsplat_amd.accel (the `dc=` rasterizer call): the split rows hold ACTIVATED values - the
+        # forward is the ordinary one on split rows, the backward gs_backward_split.  Without it split rows go with raw activations
+        self.sh_rest_activated = False
         # parity probes: keep the backward workspace (the per-Gaussian 16-slot float64 gradient rows of the blend backward)
         self.keep_workspace = False
         self.last_workspace = None
@@ -571,13 +574,16 @@ class RasterBackend:
         # (the one-shot requests of this forward are taken here, whatever follows: an empty model must not leave them armed)
         raw, self.raw_activations = self.raw_activations, False
         sh_rest, self.sh_rest = self.sh_rest, None
+        sh_activated, self.sh_rest_activated = self.sh_rest_activated, False
         self._last = None
         if P == 0:  # rasterize_points.cu:88
             self.camera_key, self.camera_key_limits, self.depth_limit_request = None, False, None
             e = torch.empty((0,), **u8)
             return (0, out_color, radii, e, e.clone(), e.clone(), out_invdepth) + tail
-        if sh_rest is not None and not raw:
-            raise RuntimeError("split SH rows are served with raw activations only (gsplat_amd.render_raw)")
+        # (split rows with ACTIVATED values: the `dc=` call of gsplat_amd.accel says so - the C forward reads them whatever `raw` is)
+        if sh_rest is not None and not raw and (not sh_activated or fsgs or extra is not None):
+            raise RuntimeError("split SH rows are served with raw activations only (gsplat_amd.render_raw), or on activated "
+                               "values by the plain rasterizer call of gsplat_amd.accel")
         if raw and fsgs:
             raise RuntimeError("raw activations do not serve the FSGS rasterizer generation")
         if (extra_gain is not None) != (raw and extra is not None):
@@ -950,11 +956,15 @@ class RasterBackend:
         arena, self.grad_arena = self.grad_arena, None
         step, self.fused_step = self.fused_step, None
         sh_rest, self.sh_rest = self.sh_rest, None
+        sh_activated, self.sh_rest_activated = self.sh_rest_activated, False
         f = self._last if self._last is not None and self._last.geom is geomBuffer else None
         if f is not None:
             raw = f.raw
-        if sh_rest is not None and (step is None or not raw or not step.grad_out_rest):
-            raise RuntimeError("split SH rows: the backward is gs_backward_step's gradients-out form with grad_out_rest")
+        # split rows: gs_backward_split on activated values (gsplat_amd.accel's `dc=` call), else the fused step's gradients-out form
+        split = sh_rest is not None and sh_activated and step is None and not raw and not fsgs and extra is None
+        if sh_rest is not None and not split and (step is None or not raw or not step.grad_out_rest):
+            raise RuntimeError("split SH rows: the backward is gs_backward_split (activated values, no 4th channel) or "
+                               "gs_backward_step's gradients-out form with grad_out_rest")
         if raw and (step is None or P == 0):
             raise RuntimeError("a forward on raw activations must be followed by the fused train-step backward")
         fused = step is not None and P != 0
@@ -1053,7 +1063,9 @@ class RasterBackend:
 
     def _backward_grads(self, arena, fsgs, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color, dL_dout_invdepth,
                         dL_dout_extra):
-        """gs_backward / _x / _fsgs: the gradients, written into the grad arena's tensors where they fit."""
+        """gs_backward / _x / _fsgs: the gradients, written into the grad arena's tensors where they fit.
+        Split SH rows (g.shs_rest): gs_backward_split - slot 5 of the tuple is the DC rows' gradient [P,1,3] and the tuple ends
+        with the rest rows' [P,M-1,3]; both are written in full by the kernel."""
         device = radii.device
         f32 = dict(dtype=torch.float32, device=device)
         # every row is written by gs_backward (culled rows become 0): empty, not zeros
@@ -1069,13 +1081,14 @@ class RasterBackend:
         # returns zero tensors for them (rasterize_points.cu:163-178) which autograd then drops
         dL_dmeans3D = out("means3D", (P, 3))
         ret = (alloc((P, 3), **f32), alloc((P, NUM_CHANNELS), **f32) if g.colors_precomp else None, alloc((P, 1), **f32),
-               dL_dmeans3D, alloc((P, 6), **f32) if g.cov3D_precomp else None, out("sh", (P, g.M, 3)), alloc((P, 3), **f32),
-               alloc((P, 4), **f32))
+               dL_dmeans3D, alloc((P, 6), **f32) if g.cov3D_precomp else None,
+               alloc((P, 1, 3), **f32) if g.shs_rest else out("sh", (P, g.M, 3)), alloc((P, 3), **f32), alloc((P, 4), **f32))
+        dsh_rest = alloc((P, g.M - 1, 3), **f32) if g.shs_rest else None
         x = dL_dout_extra is not None and not fsgs   # (a 4th channel)
         if x:
             ret = ret + (alloc((P,), **f32),)
         if P == 0:
-            return ret
+            return ret if dsh_rest is None else ret + (dsh_rest,)
         _, _, _, wsb = self.scratch_bytes(P, W, H, R)
         ws = self._fresh_workspace(device, wsb)
         s = self._scratch(geom, img, binning, self._capacity_for(binning, P, W, H, R))
@@ -1084,6 +1097,11 @@ class RasterBackend:
             ret[6].zero_()
             ret[7].zero_()
         stream = self._stream(device)
+        if dsh_rest is not None:
+            self.api.call("backward_split", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
+                          dL_dout_color.data_ptr(), _ptr(dL_dout_invdepth), C.byref(grads), dsh_rest.data_ptr(), _ptr(ws),
+                          ws.numel(), stream)
+            return ret + (dsh_rest,)
         if fsgs:
             zeros = None
             if dL_dout_invdepth is None or _prep(dL_dout_extra, device) is None:
