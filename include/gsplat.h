@@ -986,6 +986,71 @@ int gs_densify_gather(const int64_t* perm, const uint32_t* table, const float* n
                       float* new_exp_avg_sq, int32_t nfields, const int32_t* widths /*host*/, int32_t xyz_field,
                       int32_t scaling_field, float sample_div, void* stream);
 
+/* ---- FSGS's densification on the device (FSGS/scene/gaussian_model.py:424-491; the host form and arbiter is
+ * GaussianModelLite.densify_and_prune_fsgs).  Its split ORs in a distance rule over [rows | clones] and its proximity unpooling
+ * runs over the set after the split, so two gs_knn_mean_dist2_idx calls stand between the steps and the host reads counts back
+ * three times (n_clone; the merge's totals; the proximity plan's totals) to size the next buffers.  prune_on = iteration >
+ * prune_from_iter: with 0 nothing is removed, the split originals included.
+ *
+ * gs_densify_fsgs_plan (three launches): per row i of the P the flag byte GS_DENSIFY_FSGS_CLONE = |g| >= max_grad && max_scale <=
+ *   scale_bound; GRAD_SPLIT = g >= max_grad && max_scale > scale_bound; PRUNE_SELF / PRUNE_SAMPLE as GS_DENSIFY_PRUNE_*; WIDE_SELF =
+ *   max_scale > extent_bound, WIDE_SAMPLE = the same for max_k exp(log(exp(scaling_k) / sample_div)) (g, max_scale as in
+ *   gs_densify_plan; every threshold the fp32 value torch compares with).  tmp (>= gs_densify_fsgs_tmp_bytes(P) bytes, 256-byte
+ *   aligned) receives in uint32 word 0 the number of rows with CLONE; xyz1 [2 P, 3] receives the P centres and behind them the
+ *   clones' (copies of their sources') by ascending source row: the point set of kNN #1.
+ * gs_densify_fsgs_merge (two launches): dist [>= P] = kNN #1's mean squared distances; SPLIT = GRAD_SPLIT || (dist > dist_bound &&
+ *   WIDE_SELF) is written into the flag byte (a clone is never split while percent_dense <= 1: the caller's duty).  tmp words
+ *   GS_DENSIFY_FSGS_MERGE_AT .. + 4 receive [rows split, rows that stay (not split, or prune_on = 0), of those the rows the final
+ *   prune keeps, clones it keeps, split rows whose samples it keeps].
+ * gs_densify_fsgs_emit (one launch): the intermediate set Q = [rows that stay | clones | sample block 0 | ... | sample block N-1],
+ *   nQ = n_stay + n_clone + N n_split rows, no prune applied: table_q[j] = source row | kind << 30 and xyz_q[j] = the centre, the
+ *   samples' as in gs_densify_emit with noise [N n_split, 3].  The counts must be the ones in tmp, or nothing is written.
+ * gs_densify_fsgs_prox_plan (two launches): per row j of Q, from its source's flags: kept by the final prune; selected = dist[j] >
+ *   prox_bound && WIDE (of its kind), dist / nearest [nQ] / [nQ, 3] = kNN #2 on xyz_q (both NULL: no proximity); and for each of
+ *   its three neighbours whether the new row taken from it is kept (the neighbour's own prune decision).  tmp_q (>=
+ *   gs_densify_fsgs_tmp_bytes(nQ)) receives in words 0 .. 4 [kept rows of Q, selected rows S, kept new rows of neighbour 0, 1, 2].
+ * gs_densify_fsgs_final (one or two launches): the final table, P2 = n_keep_q + n_keep_prox rows in the reference's order [kept
+ *   rows of Q | kept new rows]: table[o] = source row | kind << 30 (a new row: the NEIGHBOUR's source row, kind
+ *   GS_DENSIFY_PROXIMITY, and nb_kind[o] = the neighbour's kind; 0 otherwise), new_xyz[o] = the centre.  New row m of the 3 S takes
+ *   neighbour m % 3 of selected row m / 3 and lies midway between it and selected row m % S (the reference tiles the selected
+ *   rows).  sel_rows / prox_base: [S] uint32 scratch.  The three counts must be the ones in tmp_q, or nothing is written.
+ * gs_densify_fsgs_gather (one launch): gs_densify_gather plus the proximity rows: xyz = new_xyz[e]; scaling_field = the source's,
+ *   log(exp(s) / sample_div) if nb_kind[e] is GS_DENSIFY_SAMPLE; opacity_field copied; rotation_field (1, 0, 0, 0); every other
+ *   field 0; moments +0.
+ * Errors as above: GS_E_NULL (noise only when n_split > 0; sel_rows / prox_base / nearest only when S > 0; perm never), GS_E_SHAPE
+ * (P < 1 or >= 2^29, nQ or P2 < 1 or >= 2^30, N outside 1 .. GS_DENSIFY_MAX_N, counts that are negative, too large or do not add
+ * up, field indices that coincide), GS_E_SCRATCH - all before anything is enqueued.  No atomics, no host synchronisation. */
+#define GS_DENSIFY_PROXIMITY 3
+#define GS_DENSIFY_FSGS_CLONE 1
+#define GS_DENSIFY_FSGS_GRAD_SPLIT 2
+#define GS_DENSIFY_FSGS_SPLIT 4
+#define GS_DENSIFY_FSGS_PRUNE_SELF 8
+#define GS_DENSIFY_FSGS_PRUNE_SAMPLE 16
+#define GS_DENSIFY_FSGS_WIDE_SELF 32
+#define GS_DENSIFY_FSGS_WIDE_SAMPLE 64
+#define GS_DENSIFY_FSGS_MERGE_AT 8
+size_t gs_densify_fsgs_tmp_bytes(int32_t P);
+int gs_densify_fsgs_plan(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom,
+                         const float* xyz, int32_t P, int32_t N, float max_grad, float scale_bound, float min_opacity,
+                         float world_bound, float extent_bound, float sample_div, int32_t size_test, void* tmp, size_t tmp_bytes,
+                         float* xyz1 /*[2 P, 3]*/, void* stream);
+int gs_densify_fsgs_merge(void* tmp, size_t tmp_bytes, const float* dist, int32_t P, float dist_bound, int32_t prune_on,
+                          void* stream);
+int gs_densify_fsgs_emit(const void* tmp, size_t tmp_bytes, const float* xyz, const float* scaling, const float* rotation,
+                         const float* noise, int32_t P, int32_t N, int32_t n_clone, int32_t n_split, int32_t n_stay, int32_t nQ,
+                         int32_t prune_on, uint32_t* table_q, float* xyz_q, void* stream);
+int gs_densify_fsgs_prox_plan(const void* tmp, size_t tmp_bytes, int32_t P, const uint32_t* table_q, int32_t nQ, const float* dist,
+                              const int32_t* nearest, float prox_bound, int32_t prune_on, void* tmp_q, size_t tmp_q_bytes,
+                              void* stream);
+int gs_densify_fsgs_final(const void* tmp_q, size_t tmp_q_bytes, const uint32_t* table_q, const float* xyz_q, const int32_t* nearest,
+                          int32_t nQ, int32_t n_keep_q, int32_t S, int32_t n_keep_prox, int32_t P2, uint32_t* table,
+                          uint8_t* nb_kind, float* new_xyz, uint32_t* sel_rows, uint32_t* prox_base, void* stream);
+int gs_densify_fsgs_gather(const int64_t* perm, const uint32_t* table, const uint8_t* nb_kind, const float* new_xyz, int32_t P2,
+                           const float* old_flat, const float* old_exp_avg, const float* old_exp_avg_sq, int32_t P, float* new_flat,
+                           float* new_exp_avg, float* new_exp_avg_sq, int32_t nfields, const int32_t* widths /*host*/,
+                           int32_t xyz_field, int32_t scaling_field, int32_t opacity_field, int32_t rotation_field, float sample_div,
+                           void* stream);
+
 /* ---- the visibility-sparse gradient exchange of the data-parallel step (N > 1; no reference counterpart: the reference trains
  * on one GPU).  Only Gaussians that emitted instances in SOME rank's view have a non-zero gradient row, so the ranks exchange
  * the rows of the union only.  The flat gradient buffer is field-major: field f is a [P, widths[f]] row-major block, the blocks

@@ -243,6 +243,14 @@ PROTOTYPES = {
     "densify_emit": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "morton_codes": (C.c_int, [_P, _I64, _P, _P, _P, _P]),
     "densify_gather": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, C.POINTER(C.c_int32), _I32, _I32, _F, _P]),
+    "densify_fsgs_tmp_bytes": (_SZ, [_I32]),
+    "densify_fsgs_plan": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _F, _F, _F, _F, _F, _F, _I32, _P, _SZ, _P, _P]),
+    "densify_fsgs_merge": (C.c_int, [_P, _SZ, _P, _I32, _F, _I32, _P]),
+    "densify_fsgs_emit": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
+    "densify_fsgs_prox_plan": (C.c_int, [_P, _SZ, _I32, _P, _I32, _P, _P, _F, _I32, _P, _SZ, _P]),
+    "densify_fsgs_final": (C.c_int, [_P, _SZ, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "densify_fsgs_gather": (C.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, C.POINTER(C.c_int32), _I32, _I32, _I32,
+                                      _I32, _F, _P]),
     "profile_enable": (C.c_int, [_I32]),
     "profile_only": (C.c_int, [_I32]),
     "profile_reset": (C.c_int, []),
@@ -284,6 +292,10 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # densify / split / prune on the device: GaussianModelLite.densify_and_prune's host path is the arbiter
                # (tests/densify_reference.py restates the plan in torch)
                "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather",
+               # FSGS's densification on the device: GaussianModelLite.densify_and_prune_fsgs's host path is the arbiter
+               # (tests/fsgs_densify_reference.py restates the reference's sequence in torch)
+               "densify_fsgs_tmp_bytes", "densify_fsgs_plan", "densify_fsgs_merge", "densify_fsgs_emit", "densify_fsgs_prox_plan",
+               "densify_fsgs_final", "densify_fsgs_gather",
                # test-set evaluation (PSNR / SSIM / L1 per view): restated in torch (tests/eval_reference.py)
                "eval_partials_count", "eval_tmp_bytes", "eval_metrics",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and

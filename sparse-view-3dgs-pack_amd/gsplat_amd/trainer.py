@@ -786,6 +786,225 @@ class GaussianModelLite:
             self.max_radii2D = torch.zeros((self.P,), device=self.device)
             return int(new_idx.numel())
 
+    def densify_and_prune_fsgs(self, max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres=10.0,
+                               prune_from_iter=500, proximity_until_iter=2000, generator=None, N=2, api=None, on_device=False):
+        """FSGS's own densify_and_prune (FSGS/scene/gaussian_model.py:424-491), the reference's statements in the reference's
+        order - it is NOT the 3DGS rule of densify_and_prune:
+          clone     |g| >= max_grad and max scale <= percent_dense * extent; the clones are appended (moments zero);
+          split     over the P0 + n_clone rows: (padded g >= max_grad and max scale > percent_dense * extent) OR
+                    (dist > dist_thres * extent and max scale > extent), dist = mean squared 3-NN distance of THAT point set;
+                    N samples per selected row are appended (noise from the CPU `generator`, build_rotation, scale / (0.8 N));
+                    the selected originals are removed only if iteration > prune_from_iter;
+          proximity if iteration < proximity_until_iter: the rule of proximity() on the set as it then stands (its kNN sees
+                    the split samples), tiling quirk included (see proximity's docstring);
+          prune     sigmoid(opacity) < min_opacity, with a truthy max_screen_size also max scale > 0.1 * extent (the screen
+                    rule never fires: max_radii2D has just been zeroed, as in densify_and_prune) - applied only if
+                    iteration > prune_from_iter.  FSGS/train.py:166 always passes max_screen_size = None, and its
+                    opacity threshold is prune_threshold.
+        Afterwards the Morton order is restored when spatial_order is set and the statistics are zeroed at the new size.
+        kNN: gsplat_amd.knn.dist2_with_indices(api or self.optimizer.api, ...).  The reference's `confidence` tensor (ones
+        for every new row, pruned with the rest, never read by the densification) has no counterpart on this model.
+        The whole call is ONE re-layout of parameters and moments (plus the Morton one).
+        Returns (n_clone, n_split, n_proximity, n_pruned); n_pruned counts the split originals removed and the final prune.
+        `on_device`: the same model from HIP kernels (csrc/gs_densify.hip: gs_densify_fsgs_*, _densify_fsgs_on_device) -
+        THREE host read-backs (the clone count in front of kNN #1, the split / keep counts in front of the noise and kNN #2,
+        the proximity counts that size the final buffers; two without proximity) plus the upload of the CPU-drawn noise, and one
+        gather pass; CPU-drawn noise and no atomics, so every data-parallel rank derives the same model, as with the 3DGS
+        form.  Needs a GPU model with the flat Adam state (RuntimeError otherwise).  When a kNN stage would hold
+        fewer than 4 points, every row would be pruned or percent_dense > 1, the host path runs."""
+        if self.with_nir:
+            raise NotImplementedError("densify_and_prune_fsgs: the multispectral model has no rule for the new rows' NIR albedo")
+        if on_device:
+            dev_api = getattr(self.optimizer, "api", None)
+            if not (self.flat.is_cuda and isinstance(self.optimizer, FlatAdam) and hasattr(dev_api, "_densify_fsgs_plan")):
+                raise RuntimeError("densify_and_prune_fsgs(on_device=True) needs a GPU model built with the HIP api (flat Adam "
+                                   "state); there is no fallback")
+            out = self._densify_fsgs_on_device(max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres,
+                                               prune_from_iter, proximity_until_iter, generator, N)
+            if out is not None:
+                return out
+        from .knn import dist2_with_indices
+        knn_api = api or self.optimizer.api
+        with torch.no_grad():
+            P0 = self.P
+            grads = self.xyz_gradient_accum / self.denom
+            grads[grads.isnan()] = 0.0
+            g = grads.reshape(P0)
+            dev = self.flat.device
+            cur = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
+            origin = torch.arange(P0, device=dev)      # the model's row a current row came from, -1 for an appended one
+            pruning = iteration > prune_from_iter      # prune_points (:335-336)
+            n_pruned = 0
+
+            def append(cur, origin, new):
+                n_new = new["xyz"].shape[0]
+                cur = {name: torch.cat((cur[name], new[name]), dim=0) for name in cur}
+                return cur, torch.cat((origin, torch.full((n_new,), -1, dtype=origin.dtype, device=dev)))
+
+            # densify_and_clone (:457-472)
+            max_scale = torch.exp(cur["scaling"]).max(dim=1).values
+            clone = (g.abs() >= max_grad) & (max_scale <= self.percent_dense * extent)
+            n_clone = int(clone.sum())
+            cur, origin = append(cur, origin, {name: v[clone] for name, v in cur.items()})
+            # densify_and_split (:424-454) on the P0 + n_clone rows
+            n1 = P0 + n_clone
+            padded = torch.zeros((n1,), device=dev)
+            padded[:P0] = g
+            act = torch.exp(cur["scaling"])
+            max_scale = act.max(dim=1).values
+            split = (padded >= max_grad) & (max_scale > self.percent_dense * extent)
+            dist, _ = dist2_with_indices(knn_api, cur["xyz"])
+            split = split | ((dist > dist_thres * extent) & (max_scale > extent))
+            ns = int(split.sum())
+            if ns:
+                stds = act[split].repeat(N, 1)
+                if generator is None:
+                    generator = torch.Generator().manual_seed(0)
+                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
+                samples = noise * stds
+                rots = self.build_rotation(cur["rotation"][split]).repeat(N, 1, 1)
+                new = {name: v[split].repeat(N, 1) for name, v in cur.items()}
+                new["xyz"] = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + cur["xyz"][split].repeat(N, 1)
+                new["scaling"] = torch.log(act[split].repeat(N, 1) / (0.8 * N))
+                cur, origin = append(cur, origin, new)
+                if pruning:
+                    keep = ~torch.cat((split, torch.zeros((N * ns,), dtype=torch.bool, device=dev)))
+                    cur, origin = {name: v[keep] for name, v in cur.items()}, origin[keep]
+                    n_pruned += ns
+            # proximity (:405-420) on the set as it stands
+            n_prox = 0
+            if iteration < proximity_until_iter:
+                dist, nearest = dist2_with_indices(knn_api, cur["xyz"])
+                sel = torch.logical_and(dist > (5. * extent), torch.max(torch.exp(cur["scaling"]), dim=1).values > extent)
+                new_idx = nearest[sel].reshape(-1).long()
+                source_xyz = cur["xyz"][sel].repeat(1, 3, 1).reshape(-1, 3)
+                new = {"xyz": (source_xyz + cur["xyz"][new_idx]) / 2, "scaling": cur["scaling"][new_idx],
+                       "opacity": cur["opacity"][new_idx], "features": torch.zeros_like(cur["features"][new_idx])}
+                new["rotation"] = torch.zeros_like(cur["rotation"][new_idx])
+                new["rotation"][:, 0] = 1
+                n_prox = int(new_idx.numel())
+                cur, origin = append(cur, origin, new)
+            # the final prune (:484-490)
+            prune = (torch.sigmoid(cur["opacity"]) < min_opacity).squeeze(1)
+            if max_screen_size:
+                prune = prune | (torch.exp(cur["scaling"]).max(dim=1).values > 0.1 * extent)   # (big_points_vs is all-False)
+            if pruning:
+                keep = ~prune
+                cur, origin = {name: v[keep] for name, v in cur.items()}, origin[keep]
+                n_pruned += int(prune.sum())
+            old = origin >= 0     # rows of the model come first, in their order: nothing above reorders
+            self._relayout(origin[old], {name: v[~old] for name, v in cur.items()})
+            if getattr(self, "spatial_order", False) and self.P:
+                from . import synthetic
+                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
+            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+            self.denom = torch.zeros((self.P, 1), device=self.device)
+            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            return n_clone, ns, n_prox, n_pruned
+
+    def _densify_fsgs_on_device(self, max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres, prune_from_iter,
+                                proximity_until_iter, generator, N):
+        """densify_and_prune_fsgs from the kernels of csrc/gs_densify.hip (include/gsplat.h: gs_densify_fsgs_*), the two kNN
+        searches from gs_knn_mean_dist2_idx.  Three read-backs (two without proximity), each one small copy.  Returns the
+        4-tuple, or None - nothing written, the generator untouched - when a kNN stage would hold fewer than 4 points, every row
+        would be pruned or percent_dense > 1 (a clone could then be split); the caller takes the host path."""
+        import ctypes as C
+        if self.percent_dense > 1:
+            return None
+        opt = self.optimizer
+        api, dev, P0 = opt.api, self.flat.device, self.P
+        if P0 < 1:
+            return None
+        stream = _stream_of(self.flat)
+        with torch.no_grad():
+            raw = {name: self.params[name].detach() for name, _ in self.fields}
+            accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
+            if accum.numel() != P0 or denom.numel() != P0 or accum.dtype != torch.float32 or denom.dtype != torch.float32:
+                raise RuntimeError("densification statistics do not match the model")
+            f32 = lambda v: C.c_float(v).value   # noqa: E731  (products in double, rounded once: what torch compares with)
+            sample_div = f32(0.8 * N)
+            prune_on = 1 if iteration > prune_from_iter else 0
+            proximity = iteration < proximity_until_iter
+            u8 = lambda n: torch.empty((n,), dtype=torch.uint8, device=dev)   # noqa: E731
+
+            def knn(xyz, n, with_idx):
+                dist = torch.empty((n,), dtype=torch.float32, device=dev)
+                nearest = torch.empty((n, 3), dtype=torch.int32, device=dev) if with_idx else None
+                kb = int(api.raw("knn_tmp_bytes")(n))
+                ktmp = u8(kb)
+                api.call("knn_mean_dist2_idx", xyz.data_ptr(), n, dist.data_ptr(), None if nearest is None else nearest.data_ptr(),
+                         ktmp.data_ptr(), kb, stream)
+                return dist, nearest
+
+            nbytes = api.raw("densify_fsgs_tmp_bytes")(P0)
+            tmp = u8(nbytes)
+            xyz1 = torch.empty((2 * P0, 3), dtype=torch.float32, device=dev)
+            api.call("densify_fsgs_plan", raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(),
+                     raw["xyz"].data_ptr(), P0, N, f32(max_grad), f32(self.percent_dense * extent), f32(min_opacity),
+                     f32(0.1 * extent), f32(extent), sample_div, 1 if max_screen_size else 0, tmp.data_ptr(), nbytes,
+                     xyz1.data_ptr(), stream)
+            n_clone = int(tmp[:4].view(torch.int32).cpu())                                   # read-back 1
+            if P0 + n_clone < 4:
+                return None
+            dist1, _ = knn(xyz1, P0 + n_clone, False)
+            api.call("densify_fsgs_merge", tmp.data_ptr(), nbytes, dist1.data_ptr(), P0, f32(dist_thres * extent), prune_on, stream)
+            ns, n_stay, keep_old, keep_clone, keep_split = tmp[32:52].view(torch.int32).cpu().tolist()   # read-back 2
+            nQ = n_stay + n_clone + N * ns
+            n_keep_q = keep_old + keep_clone + N * keep_split
+            # a proximity row is kept exactly when its neighbour, a row of Q, is: nothing kept in Q = nothing kept at all
+            if n_keep_q == 0 or (proximity and nQ < 4):
+                return None
+            noise = None
+            if ns:
+                if generator is None:
+                    generator = torch.Generator().manual_seed(0)
+                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
+            table_q = torch.empty((nQ,), dtype=torch.int32, device=dev)
+            xyz_q = torch.empty((nQ, 3), dtype=torch.float32, device=dev)
+            api.call("densify_fsgs_emit", tmp.data_ptr(), nbytes, raw["xyz"].data_ptr(), raw["scaling"].data_ptr(),
+                     raw["rotation"].data_ptr(), None if noise is None else noise.data_ptr(), P0, N, n_clone, ns, n_stay, nQ,
+                     prune_on, table_q.data_ptr(), xyz_q.data_ptr(), stream)
+            dist2, nearest = knn(xyz_q, nQ, True) if proximity else (None, None)
+            qbytes = api.raw("densify_fsgs_tmp_bytes")(nQ)
+            tmp_q = u8(qbytes)
+            api.call("densify_fsgs_prox_plan", tmp.data_ptr(), nbytes, P0, table_q.data_ptr(), nQ,
+                     None if dist2 is None else dist2.data_ptr(), None if nearest is None else nearest.data_ptr(),
+                     f32(5. * extent), prune_on, tmp_q.data_ptr(), qbytes, stream)
+            S, n_keep_prox = 0, 0
+            if proximity:
+                _, S, k0, k1, k2 = tmp_q[:20].view(torch.int32).cpu().tolist()              # read-back 3
+                n_keep_prox = k0 + k1 + k2
+            P2 = n_keep_q + n_keep_prox
+            table = torch.empty((P2,), dtype=torch.int32, device=dev)
+            nb_kind = u8(P2)
+            new_xyz = torch.empty((P2, 3), dtype=torch.float32, device=dev)
+            sel_rows = torch.empty((2, max(S, 1)), dtype=torch.int32, device=dev)
+            api.call("densify_fsgs_final", tmp_q.data_ptr(), qbytes, table_q.data_ptr(), xyz_q.data_ptr(),
+                     None if nearest is None else nearest.data_ptr(), nQ, n_keep_q, S, n_keep_prox, P2, table.data_ptr(),
+                     nb_kind.data_ptr(), new_xyz.data_ptr(), sel_rows[0].data_ptr(), sel_rows[1].data_ptr(), stream)
+            perm = None
+            if getattr(self, "spatial_order", False):
+                lo, hi = torch.aminmax(new_xyz, dim=0)
+                codes = torch.empty((P2,), dtype=torch.int32, device=dev)
+                api.call("morton_codes", new_xyz.data_ptr(), P2, lo.data_ptr(), hi.data_ptr(), codes.data_ptr(), stream)
+                perm = torch.sort(codes, stable=True).indices
+            old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
+            names = [name for name, _ in self.fields]
+            widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
+            self._allocate(P2)
+            opt.alloc_moments()
+            api.call("densify_fsgs_gather", None if perm is None else perm.data_ptr(), table.data_ptr(), nb_kind.data_ptr(),
+                     new_xyz.data_ptr(), P2, old_flat.data_ptr(), old_m.data_ptr(), old_v.data_ptr(), P0, self.flat.data_ptr(),
+                     opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), len(names), widths, names.index("xyz"),
+                     names.index("scaling"), names.index("opacity"), names.index("rotation"), sample_div, stream)
+            for p in self.params.values():
+                p.grad = None
+            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+            self.denom = torch.zeros((self.P, 1), device=self.device)
+            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            n_pruned = (ns + (nQ + 3 * S - P2)) if prune_on else 0
+            return n_clone, ns, 3 * S, n_pruned
+
     def reset_opacity(self):
         """gaussian_model.py:258-261: opacity <- min(opacity, 0.01), moments of that group zeroed."""
         with torch.no_grad():
@@ -1012,6 +1231,10 @@ class TrainOptions:
         self.cameras_extent = 1.0         # scene.cameras_extent = getNerfppNorm radius (dataset_readers.py:48-69)
         self.seed = 0
         self.densify_on_device = False    # densify_and_prune(on_device=True): the HIP form (GPU models only)
+        self.densify_rule = "3dgs"        # "fsgs": GaussianModelLite.densify_and_prune_fsgs (FSGS/scene/gaussian_model.py:475-491)
+        self.dist_thres = 10.0            # FSGS/arguments/__init__.py: the distance split
+        self.prune_from_iter = 500        # ... every prune_points is gated by iteration > prune_from_iter
+        self.proximity_until_iter = 2000  # FSGS/scene/gaussian_model.py:481
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option %s" % k)
@@ -1114,7 +1337,8 @@ class Trainer:
         backward, densification statistics, densify / prune / opacity reset on schedule, Adam.
         The reference replaces the parameter tensors when it densifies (their gradients are gone), so
         optimizer.step() of that iteration changes nothing; after reset_opacity only the opacity group is
-        skipped.  Returns dict(loss, densified=(n_clone, n_split, n_pruned) or None, reset=bool, P)."""
+        skipped.  Returns dict(loss, densified=(n_clone, n_split, n_pruned) or None, reset=bool, P).  With
+        opt.densify_rule = "fsgs" the densification is FSGS's (densify_and_prune_fsgs) and `densified` its 4-tuple."""
         # a step whose depth limits failed is repeated HERE, before this iteration's learning rate / SH degree exist: the
         # repeat must see the schedule state of the iteration it belongs to
         self.sync()
@@ -1148,9 +1372,18 @@ class Trainer:
             gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
             # (densify_decisions: parity instrument, see GaussianModelLite.densify_and_prune - a callable iteration -> dict)
             dec = self.densify_decisions(iteration) if self.densify_decisions is not None else None
-            densified = m.densify_and_prune(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, thr,
-                                            self.last["radii"], generator=gen, decisions=dec,
-                                            on_device=bool(getattr(opt, "densify_on_device", False)))
+            rule = getattr(opt, "densify_rule", "3dgs")
+            if rule == "fsgs":   # FSGS/train.py:166: size_threshold = None; -> (n_clone, n_split, n_proximity, n_pruned)
+                densified = m.densify_and_prune_fsgs(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
+                                                     iteration, dist_thres=opt.dist_thres, prune_from_iter=opt.prune_from_iter,
+                                                     proximity_until_iter=opt.proximity_until_iter, generator=gen,
+                                                     on_device=bool(getattr(opt, "densify_on_device", False)))
+            elif rule == "3dgs":
+                densified = m.densify_and_prune(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, thr,
+                                                self.last["radii"], generator=gen, decisions=dec,
+                                                on_device=bool(getattr(opt, "densify_on_device", False)))
+            else:
+                raise ValueError("densify_rule must be '3dgs' or 'fsgs'")
         if will_reset:
             m.reset_opacity()
             reset = True
