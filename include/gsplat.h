@@ -986,6 +986,34 @@ int gs_densify_gather(const int64_t* perm, const uint32_t* table, const float* n
                       float* new_exp_avg_sq, int32_t nfields, const int32_t* widths /*host*/, int32_t xyz_field,
                       int32_t scaling_field, float sample_div, void* stream);
 
+/* ---- DNGaussian's densification rule and its mask prunes on the device (DNGaussian/scene/gaussian_model.py:374-392, 454-524; the
+ * host forms and arbiters are GaussianModelLite.densify_and_prune_dng and GaussianModelLite.prune_points).
+ *
+ * gs_densify_plan_gated (two launches): gs_densify_plan with one more condition on GS_DENSIFY_CLONE and GS_DENSIFY_SPLIT -
+ *   sigmoid(opacity) > gate_opacity (the reference's get_opacity > opa_thresh; the sigmoid is the value the min_opacity test is
+ *   taken on, the threshold the fp32 value torch compares with; a NaN opacity selects nothing).  The prune flags, the layout of
+ *   tmp (gs_densify_tmp_bytes) and the five totals are gs_densify_plan's, so gs_densify_emit, gs_morton_codes and
+ *   gs_densify_gather follow unchanged.  With gate_opacity < 0 the bytes of tmp are gs_densify_plan's.
+ * gs_prune_plan (two launches): mask [P] bytes, nonzero = the row goes.  tmp (>= gs_prune_tmp_bytes(P) bytes, 256-byte aligned)
+ *   receives in word 0 (uint32) the number of rows kept - the one value the host reads -, behind byte 256 the rows kept per
+ *   256-row block and their exclusive prefixes over the blocks (private to gs_prune_emit).
+ * gs_prune_emit (one launch): the P2 kept rows in their old relative order: table[j] = source row | GS_DENSIFY_SURVIVOR << 30,
+ *   new_xyz[j] = a copy of the row's centre, and new_xyz_gradient_accum / new_denom / new_max_radii2D [P2] = the source's
+ *   statistics (a prune indexes them, it does not zero them).  P2 must be the total in tmp: the kernel compares and writes nothing
+ *   if they differ.  The parameters and both moments then go through gs_densify_gather with that table (perm = NULL: a subsequence
+ *   of spatially ordered rows is ordered); no row is a sample, so its sample_div is not read.
+ * GS_E_NULL: a pointer is missing; GS_E_SHAPE: P < 1 or >= 2^30, N outside 1 .. GS_DENSIFY_MAX_N, P2 < 1 or > P; GS_E_SCRATCH:
+ * tmp_bytes too small - all before any launch.  Enqueued on `stream`, no host synchronisation, no atomics: the same inputs give
+ * the same bits. */
+int gs_densify_plan_gated(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P,
+                          int32_t N, float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div,
+                          int32_t size_test, float gate_opacity, void* tmp, size_t tmp_bytes, void* stream);
+size_t gs_prune_tmp_bytes(int32_t P);
+int gs_prune_plan(const uint8_t* mask, int32_t P, void* tmp, size_t tmp_bytes, void* stream);
+int gs_prune_emit(const void* tmp, size_t tmp_bytes, const uint8_t* mask, const float* xyz, int32_t P, int32_t P2, uint32_t* table,
+                  float* new_xyz, const float* xyz_gradient_accum, const float* denom, const float* max_radii2D,
+                  float* new_xyz_gradient_accum, float* new_denom, float* new_max_radii2D, void* stream);
+
 /* ---- FSGS's densification on the device (FSGS/scene/gaussian_model.py:424-491; the host form and arbiter is
  * GaussianModelLite.densify_and_prune_fsgs).  Its split ORs in a distance rule over [rows | clones] and its proximity unpooling
  * runs over the set after the split, so two gs_knn_mean_dist2_idx calls stand between the steps and the host reads counts back

@@ -19,6 +19,11 @@
 // on every run and on every data-parallel rank.  Compiled with -ffp-contract=off: the plan's comparisons and the float64 Morton
 // arithmetic are single roundings that restate torch's.
 //
+// DNGaussian's rule (DNGaussian/scene/gaussian_model.py:454-524, GaussianModelLite.densify_and_prune_dng) is the same plan with one
+// more condition on clone and split, sigmoid(opacity) > opa_thresh (gs_densify_plan_gated): still a per-source-row decision, since
+// the gate reads the source's own opacity.  Its mask prunes (prune_points: near-camera, unseen, opacity) are a plan / emit pair of
+// their own in front of the same gather (gs_prune_plan / gs_prune_emit).
+//
 // The second half of the file is FSGS's densification (FSGS/scene/gaussian_model.py:424-491, the device form of
 // GaussianModelLite.densify_and_prune_fsgs): the same building blocks, but its stages hang on two kNN searches (see there).
 #include <math.h>
@@ -67,8 +72,8 @@ static __device__ __forceinline__ void dn_preds(unsigned f, bool in, bool* c) {
 __global__ void __launch_bounds__(DN_BLOCK) densify_plan_kernel(const float* __restrict__ scaling, const float* __restrict__ opacity,
                                                                const float* __restrict__ accum, const float* __restrict__ denom, int P,
                                                                float max_grad, float scale_bound, float min_opacity, float world_bound,
-                                                               float sample_div, int size_test, uint8_t* __restrict__ flags,
-                                                               uint32_t* __restrict__ counts) {
+                                                               float sample_div, int size_test, int gated, float gate_opacity,
+                                                               uint8_t* __restrict__ flags, uint32_t* __restrict__ counts) {
   __shared__ uint32_t s_cnt[DN_WAVES][DN_NC];
   const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;   // (size_t: 4 i passes 2^31 long before i does)
   const bool in = i < (size_t)P;
@@ -84,8 +89,10 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_plan_kernel(const float* __r
     // the chain the host evaluates on the new rows: exp(log(exp(s) / (0.8 N)))
     const float m0 = expf(logf(e0 / sample_div)), m1 = expf(logf(e1 / sample_div)), m2 = expf(logf(e2 / sample_div));
     const float max_sample = fmaxf(fmaxf(m0, m1), m2);
-    if (fabsf(g) >= max_grad && small) f |= GS_DENSIFY_CLONE;
-    if (g >= max_grad && !small) f |= GS_DENSIFY_SPLIT;
+    // DNGaussian's rule (gs_densify_plan_gated): clone and split also need get_opacity > opa_thresh; a NaN opacity selects nothing
+    const bool open = !gated || op > gate_opacity;
+    if (fabsf(g) >= max_grad && small && open) f |= GS_DENSIFY_CLONE;
+    if (g >= max_grad && !small && open) f |= GS_DENSIFY_SPLIT;
     if (faint || (size_test && max_scale > world_bound)) f |= GS_DENSIFY_PRUNE_SELF;
     if (faint || (size_test && max_sample > world_bound)) f |= GS_DENSIFY_PRUNE_SAMPLE;
     flags[i] = (uint8_t)f;
@@ -339,13 +346,79 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_gather_kernel(const long lon
 #undef DN_GATHER
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The mask prune (DNGaussian/scene/gaussian_model.py:374-392, the device form of GaussianModelLite.prune_points): the rows whose
+// mask byte is 0, in their old order.  plan: rows kept per 256-row block, in the DN_NC-strided count layout so that the one-workgroup
+// scan above serves it unchanged (columns 1 .. 4 stay 0); emit: destination = block prefix + ballot / popcount rank, the table
+// entry (a survivor), the centre, and the three densification statistics, which a prune indexes and does not zero.  The
+// parameters and moments then go through densify_gather_kernel with that table.
+// ------------------------------------------------------------------------------------------------------------------
+struct PruneTmp {
+  uint32_t* totals;  // [DN_NC] in the first 256 bytes: word 0 = rows kept
+  uint32_t* counts;  // [nb][DN_NC]
+  uint32_t* prefix;  // [nb][DN_NC]
+};
+static inline size_t pr_tmp_bytes(size_t P) { return 256 + 2 * gs_align(4 * DN_NC * dn_blocks(P)); }
+static inline PruneTmp pr_tmp_view(void* buf, size_t P) {
+  char* p = (char*)buf;
+  PruneTmp t;
+  t.totals = (uint32_t*)p; p += 256;
+  t.counts = (uint32_t*)p; p += gs_align(4 * DN_NC * dn_blocks(P));
+  t.prefix = (uint32_t*)p;
+  return t;
+}
+
+__global__ void __launch_bounds__(DN_BLOCK) prune_plan_kernel(const uint8_t* __restrict__ mask, int P, uint32_t* __restrict__ counts) {
+  __shared__ uint32_t s_cnt[DN_WAVES];
+  const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+  const bool keep = i < (size_t)P && mask[i] == 0;
+  const unsigned long long b = __ballot(keep);
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x < DN_NC) {
+    uint32_t s = 0;
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int w = 0; w < DN_WAVES; w++) s += s_cnt[w];
+    counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = s;
+  }
+}
+
+__global__ void __launch_bounds__(DN_BLOCK) prune_emit_kernel(const uint8_t* __restrict__ mask, const uint32_t* __restrict__ prefix,
+                                                             const uint32_t* __restrict__ totals, const float* __restrict__ xyz,
+                                                             const float* __restrict__ accum, const float* __restrict__ denom,
+                                                             const float* __restrict__ radii, int P, uint32_t P2,
+                                                             uint32_t* __restrict__ table, float* __restrict__ new_xyz,
+                                                             float* __restrict__ new_accum, float* __restrict__ new_denom,
+                                                             float* __restrict__ new_radii) {
+  __shared__ uint32_t s_cnt[DN_WAVES];
+  // the count the host sized the outputs with must be the plan's (uniform over the grid: nobody reaches the barrier)
+  if (totals[0] != P2) return;
+  const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
+  const bool keep = i < (size_t)P && mask[i] == 0;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned long long b = __ballot(keep);
+  uint32_t rank = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+  if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(b);
+  __syncthreads();
+  for (int w = 0; w < wave; w++) rank += s_cnt[w];
+  if (!keep) return;
+  const size_t j = (size_t)prefix[(size_t)blockIdx.x * DN_NC] + rank;   // ascending source row: the old relative order
+  if (j >= (size_t)P2) return;
+  table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SURVIVOR << DN_KIND_SHIFT);
+  new_xyz[3 * j] = xyz[3 * i]; new_xyz[3 * j + 1] = xyz[3 * i + 1]; new_xyz[3 * j + 2] = xyz[3 * i + 2];
+  new_accum[j] = accum[i];
+  new_denom[j] = denom[i];
+  new_radii[j] = radii[i];
+}
+
 extern "C" {
 
 size_t gs_densify_tmp_bytes(int32_t P) { return P < 1 ? 0 : dn_tmp_bytes((size_t)P); }
 
-int gs_densify_plan(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P,
-                    int32_t N, float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div,
-                    int32_t size_test, void* tmp, size_t tmp_bytes, void* stream) {
+static int dn_plan(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P, int32_t N,
+                   float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div, int32_t size_test,
+                   int gated, float gate_opacity, void* tmp, size_t tmp_bytes, void* stream) {
   if (!scaling || !opacity || !xyz_gradient_accum || !denom || !tmp) return GS_E_NULL;
   if (P < 1 || P > (int32_t)DN_ROW_MASK || N < 1 || N > GS_DENSIFY_MAX_N) return GS_E_SHAPE;
   if (tmp_bytes < dn_tmp_bytes((size_t)P)) return GS_E_SCRATCH;
@@ -354,10 +427,24 @@ int gs_densify_plan(const float* scaling, const float* opacity, const float* xyz
   hipStream_t s = (hipStream_t)stream;
   GS_PROF(ST_MODEL, s);
   hipLaunchKernelGGL(densify_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, scaling, opacity, xyz_gradient_accum, denom, P, max_grad,
-                     scale_bound, min_opacity, world_bound, sample_div, size_test ? 1 : 0, t.flags, t.counts);
+                     scale_bound, min_opacity, world_bound, sample_div, size_test ? 1 : 0, gated, gate_opacity, t.flags, t.counts);
   hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(DN_BLOCK), 0, s, t.counts, nb, t.prefix, t.totals);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
+}
+
+int gs_densify_plan(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P,
+                    int32_t N, float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div,
+                    int32_t size_test, void* tmp, size_t tmp_bytes, void* stream) {
+  return dn_plan(scaling, opacity, xyz_gradient_accum, denom, P, N, max_grad, scale_bound, min_opacity, world_bound, sample_div,
+                 size_test, 0, 0.0f, tmp, tmp_bytes, stream);
+}
+
+int gs_densify_plan_gated(const float* scaling, const float* opacity, const float* xyz_gradient_accum, const float* denom, int32_t P,
+                          int32_t N, float max_grad, float scale_bound, float min_opacity, float world_bound, float sample_div,
+                          int32_t size_test, float gate_opacity, void* tmp, size_t tmp_bytes, void* stream) {
+  return dn_plan(scaling, opacity, xyz_gradient_accum, denom, P, N, max_grad, scale_bound, min_opacity, world_bound, sample_div,
+                 size_test, 1, gate_opacity, tmp, tmp_bytes, stream);
 }
 
 int gs_densify_emit(const void* tmp, size_t tmp_bytes, const float* xyz, const float* scaling, const float* rotation,
@@ -421,6 +508,40 @@ int gs_densify_gather(const int64_t* perm, const uint32_t* table, const float* n
   hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)dn_blocks((size_t)P2), (unsigned)nfields), dim3(DN_BLOCK), 0, s,
                      (const long long*)perm, table, new_xyz, (uint32_t)P2, old_flat, old_exp_avg, old_exp_avg_sq, (uint32_t)P, new_flat,
                      new_exp_avg, new_exp_avg_sq, f, sample_div);
+  GS_LAUNCH_CHECK(s, 0);
+  return GS_OK;
+}
+
+size_t gs_prune_tmp_bytes(int32_t P) { return P < 1 ? 0 : pr_tmp_bytes((size_t)P); }
+
+int gs_prune_plan(const uint8_t* mask, int32_t P, void* tmp, size_t tmp_bytes, void* stream) {
+  if (!mask || !tmp) return GS_E_NULL;
+  if (P < 1 || P > (int32_t)DN_ROW_MASK) return GS_E_SHAPE;
+  if (tmp_bytes < pr_tmp_bytes((size_t)P)) return GS_E_SCRATCH;
+  const PruneTmp t = pr_tmp_view(tmp, (size_t)P);
+  const int nb = (int)dn_blocks((size_t)P);
+  hipStream_t s = (hipStream_t)stream;
+  GS_PROF(ST_MODEL, s);
+  hipLaunchKernelGGL(prune_plan_kernel, dim3(nb), dim3(DN_BLOCK), 0, s, mask, P, t.counts);
+  hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(DN_BLOCK), 0, s, t.counts, nb, t.prefix, t.totals);
+  GS_LAUNCH_CHECK(s, 0);
+  return GS_OK;
+}
+
+int gs_prune_emit(const void* tmp, size_t tmp_bytes, const uint8_t* mask, const float* xyz, int32_t P, int32_t P2, uint32_t* table,
+                  float* new_xyz, const float* xyz_gradient_accum, const float* denom, const float* max_radii2D,
+                  float* new_xyz_gradient_accum, float* new_denom, float* new_max_radii2D, void* stream) {
+  if (!tmp || !mask || !xyz || !table || !new_xyz || !xyz_gradient_accum || !denom || !max_radii2D || !new_xyz_gradient_accum ||
+      !new_denom || !new_max_radii2D)
+    return GS_E_NULL;
+  if (P < 1 || P > (int32_t)DN_ROW_MASK || P2 < 1 || P2 > P) return GS_E_SHAPE;
+  if (tmp_bytes < pr_tmp_bytes((size_t)P)) return GS_E_SCRATCH;
+  const PruneTmp t = pr_tmp_view(const_cast<void*>(tmp), (size_t)P);
+  hipStream_t s = (hipStream_t)stream;
+  GS_PROF(ST_MODEL, s);
+  hipLaunchKernelGGL(prune_emit_kernel, dim3((unsigned)dn_blocks((size_t)P)), dim3(DN_BLOCK), 0, s, mask, t.prefix, t.totals, xyz,
+                     xyz_gradient_accum, denom, max_radii2D, P, (uint32_t)P2, table, new_xyz, new_xyz_gradient_accum, new_denom,
+                     new_max_radii2D);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
 }

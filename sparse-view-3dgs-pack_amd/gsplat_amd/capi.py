@@ -243,6 +243,10 @@ PROTOTYPES = {
     "densify_emit": (C.c_int, [_P, _SZ, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P]),
     "morton_codes": (C.c_int, [_P, _I64, _P, _P, _P, _P]),
     "densify_gather": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I32, _P, _P, _P, _I32, C.POINTER(C.c_int32), _I32, _I32, _F, _P]),
+    "densify_plan_gated": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _F, _F, _F, _F, _F, _I32, _F, _P, _SZ, _P]),
+    "prune_tmp_bytes": (_SZ, [_I32]),
+    "prune_plan": (C.c_int, [_P, _I32, _P, _SZ, _P]),
+    "prune_emit": (C.c_int, [_P, _SZ, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "densify_fsgs_tmp_bytes": (_SZ, [_I32]),
     "densify_fsgs_plan": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _F, _F, _F, _F, _F, _F, _I32, _P, _SZ, _P, _P]),
     "densify_fsgs_merge": (C.c_int, [_P, _SZ, _P, _I32, _F, _I32, _P]),
@@ -296,6 +300,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                # (tests/fsgs_densify_reference.py restates the reference's sequence in torch)
                "densify_fsgs_tmp_bytes", "densify_fsgs_plan", "densify_fsgs_merge", "densify_fsgs_emit", "densify_fsgs_prox_plan",
                "densify_fsgs_final", "densify_fsgs_gather",
+               # DNGaussian's rule and its mask prunes on the device: GaussianModelLite.densify_and_prune_dng / prune_points' host
+               # paths are the arbiters (tests/dng_densify_reference.py restates the reference's sequence in torch)
+               "densify_plan_gated", "prune_tmp_bytes", "prune_plan", "prune_emit",
                # test-set evaluation (PSNR / SSIM / L1 per view): restated in torch (tests/eval_reference.py)
                "eval_partials_count", "eval_tmp_bytes", "eval_metrics",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and

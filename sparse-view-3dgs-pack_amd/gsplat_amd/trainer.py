@@ -693,10 +693,11 @@ class GaussianModelLite:
             self.max_radii2D = torch.zeros((self.P,), device=self.device)
             return int(ci.numel()), ns, int(prune.sum())
 
-    def _densify_on_device(self, max_grad, min_opacity, extent, max_screen_size, generator, N):
+    def _densify_on_device(self, max_grad, min_opacity, extent, max_screen_size, generator, N, gate_opacity=None):
         """densify_and_prune from the kernels of csrc/gs_densify.hip (include/gsplat.h: gs_densify_plan / emit / gather,
         gs_morton_codes).  Returns (n_clone, n_split, n_pruned), or None - nothing written, the generator untouched - when every
-        row would be pruned (the caller then takes the host path)."""
+        row would be pruned (the caller then takes the host path).  gate_opacity (DNGaussian's rule, _densify_dng_on_device):
+        the plan is gs_densify_plan_gated's; everything behind it is unchanged."""
         import ctypes as C
         opt = self.optimizer
         api, dev, P0 = opt.api, self.flat.device, self.P
@@ -712,9 +713,12 @@ class GaussianModelLite:
             sample_div = f32(0.8 * N)
             nbytes = api.raw("densify_tmp_bytes")(P0)
             tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            api.call("densify_plan", raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(), P0, N,
-                     f32(max_grad), f32(self.percent_dense * extent), f32(min_opacity), f32(0.1 * extent), sample_div,
-                     1 if max_screen_size else 0, tmp.data_ptr(), nbytes, stream)
+            plan = [raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(), P0, N, f32(max_grad),
+                    f32(self.percent_dense * extent), f32(min_opacity), f32(0.1 * extent), sample_div, 1 if max_screen_size else 0]
+            if gate_opacity is None:
+                api.call("densify_plan", *plan, tmp.data_ptr(), nbytes, stream)
+            else:
+                api.call("densify_plan_gated", *plan, f32(gate_opacity), tmp.data_ptr(), nbytes, stream)
             # the ONE read-back: the counts size the new buffers and the noise (whose upload below blocks too, when rows split)
             n_keep, n_clone_keep, ns, ns_keep, n_clone = tmp[:20].view(torch.int32).cpu().tolist()
             P2 = n_keep + n_clone_keep + N * ns_keep
@@ -750,6 +754,182 @@ class GaussianModelLite:
             self.denom = torch.zeros((self.P, 1), device=self.device)
             self.max_radii2D = torch.zeros((self.P,), device=self.device)
             return n_clone, ns, (P0 - ns - n_keep) + (n_clone - n_clone_keep) + N * (ns - ns_keep)
+
+    # ------------------------------------------------------------------ DNGaussian: mask prunes and its densification rule
+    def _require_device_form(self, what, entry):
+        api = getattr(self.optimizer, "api", None)
+        if not (self.flat.is_cuda and isinstance(self.optimizer, FlatAdam) and hasattr(api, "_" + entry)):
+            raise RuntimeError("%s(on_device=True) needs a GPU model built with the HIP api (flat Adam state); "
+                               "there is no fallback" % what)
+
+    def prune_points(self, mask, on_device=False):
+        """DNGaussian/scene/gaussian_model.py:374-392: remove the rows whose mask entry is nonzero (bool or uint8, [P] or
+        [P,1]).  The new model is the rows that stay, in their old relative order (a subsequence of spatially ordered rows is
+        ordered: nothing is re-sorted); parameters and both Adam moments are copied bit for bit (_prune_optimizer), and
+        xyz_gradient_accum, denom and max_radii2D are INDEXED, not zeroed (:387-392) - a prune between two densifications keeps
+        what the views since the last one have accumulated.  Step counts stay, every p.grad is None afterwards, the dormant
+        flags are recomputed.  The multispectral model's NIR field is one more copied field.  Returns the number of rows removed;
+        an all-false mask returns 0 and touches nothing (`generation` does not move).
+        `on_device`: the same model from gs_prune_plan / gs_prune_emit and the gather of the densification
+        (csrc/gs_densify.hip), ONE host read-back (the number of rows kept, which sizes the new buffers) where the host path
+        has the nonzero() of its boolean index.  Needs a GPU model with the flat Adam state (RuntimeError otherwise); when every
+        row goes, the host path runs."""
+        if on_device:
+            self._require_device_form("prune_points", "prune_plan")
+        P0 = self.P
+        mask = torch.as_tensor(mask)
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("prune_points: the mask must be bool or uint8, got %s" % mask.dtype)
+        if tuple(mask.shape) not in ((P0,), (P0, 1)):
+            raise ValueError("prune_points: the mask must be [P] or [P,1] with P = %d, got shape %s" % (P0, tuple(mask.shape)))
+        if not isinstance(self.optimizer, FlatAdam):
+            raise NotImplementedError("prune_points needs the flat Adam state")
+        with torch.no_grad():
+            mask = mask.reshape(P0).to(self.flat.device)
+            remove = mask if mask.dtype == torch.bool else mask != 0
+            if on_device and P0 > 0:
+                out = self._prune_on_device(remove)
+                if out is not None:
+                    return out
+            src = (~remove).nonzero().squeeze(1)
+            n_removed = P0 - int(src.numel())
+            if n_removed == 0:
+                return 0
+            accum, denom, radii = self.xyz_gradient_accum[src], self.denom[src], self.max_radii2D[src]
+            self._relayout(src, {})
+            self.xyz_gradient_accum, self.denom, self.max_radii2D = accum, denom, radii
+            return n_removed
+
+    def _prune_on_device(self, remove):
+        """prune_points from gs_prune_plan / gs_prune_emit / gs_densify_gather.  `remove`: bool [P] on the model's device.
+        Returns the number of rows removed, or None - nothing written - when every row would go."""
+        import ctypes as C
+        opt = self.optimizer
+        api, dev, P0 = opt.api, self.flat.device, self.P
+        stream = _stream_of(self.flat)
+        remove = remove.contiguous()
+        stats = [self.xyz_gradient_accum.contiguous(), self.denom.contiguous(), self.max_radii2D.contiguous()]
+        if any(t.numel() != P0 or t.dtype != torch.float32 or t.device != dev for t in stats):
+            raise RuntimeError("densification statistics do not match the model")
+        nbytes = api.raw("prune_tmp_bytes")(P0)
+        tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        api.call("prune_plan", remove.data_ptr(), P0, tmp.data_ptr(), nbytes, stream)
+        P2 = int(tmp[:4].view(torch.int32).cpu())   # the ONE read-back: the number of rows kept sizes the new buffers
+        if P2 == 0:
+            return None
+        if P2 == P0:
+            return 0
+        table = torch.empty((P2,), dtype=torch.int32, device=dev)
+        new_xyz = torch.empty((P2, 3), dtype=torch.float32, device=dev)
+        new_stats = [torch.empty((P2, 1), device=dev), torch.empty((P2, 1), device=dev), torch.empty((P2,), device=dev)]
+        api.call("prune_emit", tmp.data_ptr(), nbytes, remove.data_ptr(), self.params["xyz"].detach().data_ptr(), P0, P2,
+                 table.data_ptr(), new_xyz.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
+                 new_stats[0].data_ptr(), new_stats[1].data_ptr(), new_stats[2].data_ptr(), stream)
+        old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
+        names = [name for name, _ in self.fields]
+        widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
+        self._allocate(P2)
+        opt.alloc_moments()
+        # every row is a survivor: no sample, so the gather's sample_div is never read
+        api.call("densify_gather", None, table.data_ptr(), new_xyz.data_ptr(), P2, old_flat.data_ptr(), old_m.data_ptr(),
+                 old_v.data_ptr(), P0, self.flat.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), len(names), widths,
+                 names.index("xyz"), names.index("scaling"), 1.0, stream)
+        for p in self.params.values():  # replaced tensors have no gradient until the next backward
+            p.grad = None
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = new_stats
+        return P0 - P2
+
+    def prune(self, min_opacity, on_device=False):
+        """DNGaussian/scene/gaussian_model.py:536-538: prune_points(sigmoid(opacity) < min_opacity).  The mask is formed on the
+        model's device with no read-back; the prune's count is the only one.  Returns the number of rows removed."""
+        with torch.no_grad():
+            mask = (self.get_opacity < min_opacity).squeeze(1)
+        return self.prune_points(mask, on_device=on_device)
+
+    def densify_and_prune_dng(self, max_grad, min_opacity, extent, max_screen_size, opa_thresh, max_dist=None, generator=None,
+                              N=2, on_device=False):
+        """DNGaussian's densify_and_prune (DNGaussian/scene/gaussian_model.py:454-524), the reference's statements in the
+        reference's order - the 3DGS rule of densify_and_prune with three differences:
+          outliers  if max_dist is not None (a float, or a tensor of P elements): rows with sqrt(distCUDA2(xyz)) > max_dist are
+                    removed FIRST, through prune_points - so the statistics the selection reads are those of the rows that stay;
+          gate      clone (|g| >= max_grad, max scale <= percent_dense * extent) and split (g >= max_grad, larger) both ALSO
+                    need sigmoid(opacity) > opa_thresh; a clone is never split; samples use scale / (0.8 N);
+          prune     sigmoid(opacity) < min_opacity ONLY: the reference's max_screen_size branch reads max_radii2D, which
+                    densification_postfix has just zeroed, so it never fires (as in densify_and_prune) and there is no world-size
+                    rule beside it.  Reproduced by construction: max_screen_size is accepted and not read.
+        Then the statistics are zeroed at the new size.  Selection, split and final prune are ONE re-layout
+        ([survivors | clones | sample blocks], then the Morton order under spatial_order) where the reference re-creates the
+        optimizer state four times; the outlier prune in front is a second one.  Noise: CPU randn from `generator` times the stds,
+        as densify_and_prune draws it.  Returns (n_outliers, n_clone, n_split, n_pruned); n_pruned counts the final prune.
+        `on_device`: the same model from HIP kernels - gs_densify_plan_gated, then gs_densify_emit / gs_morton_codes /
+        gs_densify_gather unchanged: one count read-back, the noise upload the only other wait.  max_dist composes
+        gs_knn_mean_dist2, torch's sqrt and compare on the device and prune_points(on_device=True) (one more read-back).  Needs a
+        GPU model with the flat Adam state (RuntimeError otherwise); when every row would be pruned the host path runs."""
+        if on_device:
+            self._require_device_form("densify_and_prune_dng", "densify_plan_gated")
+        n_outliers = 0
+        if max_dist is not None:
+            from .knn import dist2
+            with torch.no_grad():
+                dist = torch.sqrt(dist2(self.optimizer.api, self.params["xyz"].detach()))
+                if torch.is_tensor(max_dist):
+                    if max_dist.numel() != self.P:
+                        raise ValueError("densify_and_prune_dng: max_dist must be a number or hold P = %d elements" % self.P)
+                    max_dist = max_dist.reshape(self.P).to(dist.device)
+                outliers = dist > max_dist
+            n_outliers = self.prune_points(outliers, on_device=on_device)
+        if on_device and self.P > 0:
+            out = self._densify_dng_on_device(max_grad, min_opacity, extent, opa_thresh, generator, N)
+            if out is not None:
+                return (n_outliers,) + out
+        with torch.no_grad():
+            P0 = self.P
+            grads = self.xyz_gradient_accum / self.denom
+            grads[grads.isnan()] = 0.0
+            g = grads.reshape(P0)
+            scaling = self.get_scaling
+            small = scaling.max(dim=1).values <= self.percent_dense * extent
+            gate = self.get_opacity.squeeze(1) > opa_thresh
+            clone = (g.abs() >= max_grad) & small & gate
+            split = (g >= max_grad) & ~small & gate      # padded_grad of the clones is 0: never selected
+            ci = clone.nonzero().squeeze(1)
+            si = split.nonzero().squeeze(1)
+            ns = int(si.numel())
+            raw = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
+            new = {name: [raw[name][ci]] for name, _ in self.fields}
+            if ns:
+                stds = scaling[si].repeat(N, 1)
+                if generator is None:
+                    generator = torch.Generator().manual_seed(0)
+                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(stds.device)
+                samples = noise * stds
+                rots = self.build_rotation(raw["rotation"][si]).repeat(N, 1, 1)
+                new["xyz"].append(torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + raw["xyz"][si].repeat(N, 1))
+                new["scaling"].append(torch.log(scaling[si].repeat(N, 1) / (0.8 * N)))
+                for name, _ in self.fields:
+                    if name not in ("xyz", "scaling"):
+                        new[name].append(raw[name][si].repeat(N, 1))
+            new = {name: torch.cat(v, dim=0) for name, v in new.items()}
+            # final prune (:518-523) evaluated on [survivors, clones, samples]: opacity only
+            keep_old = ~split
+            op_all = torch.cat((torch.sigmoid(raw["opacity"][keep_old]), torch.sigmoid(new["opacity"])), dim=0).squeeze(1)
+            prune = op_all < min_opacity
+            n_keep_old = int(keep_old.sum())
+            src = keep_old.nonzero().squeeze(1)[~prune[:n_keep_old]]
+            keep_new = ~prune[n_keep_old:]
+            self._relayout(src, {name: v[keep_new] for name, v in new.items()})
+            if getattr(self, "spatial_order", False) and self.P > 0:   # the new rows go where their neighbours are
+                from . import synthetic
+                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
+            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+            self.denom = torch.zeros((self.P, 1), device=self.device)
+            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            return n_outliers, int(ci.numel()), ns, int(prune.sum())
+
+    def _densify_dng_on_device(self, max_grad, min_opacity, extent, opa_thresh, generator, N):
+        """Steps 2-6 of densify_and_prune_dng from the kernels: _densify_on_device with the gated plan and no size test.
+        Returns (n_clone, n_split, n_pruned), or None when every row would be pruned."""
+        return self._densify_on_device(max_grad, min_opacity, extent, None, generator, N, gate_opacity=opa_thresh)
 
     def proximity(self, extent, api=None):
         """FSGS's proximity-guided unpooling (FSGS/scene/gaussian_model.py:405-420, N = 3), the reference's tensor
@@ -1005,11 +1185,19 @@ class GaussianModelLite:
             n_pruned = (ns + (nQ + 3 * S - P2)) if prune_on else 0
             return n_clone, ns, 3 * S, n_pruned
 
-    def reset_opacity(self):
-        """gaussian_model.py:258-261: opacity <- min(opacity, 0.01), moments of that group zeroed."""
+    def reset_opacity(self, value=0.01):
+        """gaussian_model.py:258-261: opacity <- min(opacity, 0.01), moments of that group zeroed.  `value`: DNGaussian's
+        form (DNGaussian/scene/gaussian_model.py:296-300) takes the ceiling as an argument."""
+        self._clamp_opacity(torch.minimum, value)
+
+    def reset_opacity_max(self, value=0.8):
+        """DNGaussian/scene/gaussian_model.py:302-306: opacity <- max(opacity, value), moments of that group zeroed."""
+        self._clamp_opacity(torch.maximum, value)
+
+    def _clamp_opacity(self, bound, value):
         with torch.no_grad():
             op = torch.sigmoid(self.params["opacity"])
-            new = torch.minimum(op, torch.full_like(op, 0.01))
+            new = bound(op, torch.full_like(op, value))
             self.params["opacity"].copy_(torch.log(new / (1 - new)))
             opt = self.optimizer
             opt.field_views(opt.exp_avg)["opacity"].zero_()
@@ -1232,9 +1420,11 @@ class TrainOptions:
         self.seed = 0
         self.densify_on_device = False    # densify_and_prune(on_device=True): the HIP form (GPU models only)
         self.densify_rule = "3dgs"        # "fsgs": GaussianModelLite.densify_and_prune_fsgs (FSGS/scene/gaussian_model.py:475-491)
+        #                                   "dng": densify_and_prune_dng (DNGaussian/scene/gaussian_model.py:507-524)
         self.dist_thres = 10.0            # FSGS/arguments/__init__.py: the distance split
         self.prune_from_iter = 500        # ... every prune_points is gated by iteration > prune_from_iter
         self.proximity_until_iter = 2000  # FSGS/scene/gaussian_model.py:481
+        self.split_opacity_thresh = 0.1   # DNGaussian/arguments/__init__.py:93: densify_rule = "dng" clones / splits above it only
         for k, v in kw.items():
             if not hasattr(self, k):
                 raise TypeError("unknown option %s" % k)
@@ -1328,6 +1518,7 @@ class Trainer:
         return mine
 
     densify_decisions = None
+    last_options = None   # the TrainOptions of the last train_iteration (prune_near_cameras / prune_unseen: on_device=None)
     alpha_masks = None
     _bg_gen = None
     _use_stage = False   # (set per step by _step_camera: exposure / alpha mask inside the criterion's node)
@@ -1338,10 +1529,12 @@ class Trainer:
         The reference replaces the parameter tensors when it densifies (their gradients are gone), so
         optimizer.step() of that iteration changes nothing; after reset_opacity only the opacity group is
         skipped.  Returns dict(loss, densified=(n_clone, n_split, n_pruned) or None, reset=bool, P).  With
-        opt.densify_rule = "fsgs" the densification is FSGS's (densify_and_prune_fsgs) and `densified` its 4-tuple."""
+        opt.densify_rule = "fsgs" the densification is FSGS's (densify_and_prune_fsgs) and `densified` its 4-tuple; with "dng" it
+        is DNGaussian's (densify_and_prune_dng) and `densified` is (n_outliers, n_clone, n_split, n_pruned)."""
         # a step whose depth limits failed is repeated HERE, before this iteration's learning rate / SH degree exist: the
         # repeat must see the schedule state of the iteration it belongs to
         self.sync()
+        self.last_options = opt
         m = self.model
         m.update_learning_rate(iteration, opt.position_lr_final, opt.position_lr_delay_mult, opt.position_lr_max_steps,
                                exposure_max_steps=opt.iterations)
@@ -1382,8 +1575,12 @@ class Trainer:
                 densified = m.densify_and_prune(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, thr,
                                                 self.last["radii"], generator=gen, decisions=dec,
                                                 on_device=bool(getattr(opt, "densify_on_device", False)))
+            elif rule == "dng":   # DNGaussian/train_llff.py:199-201: size_threshold = max_dist = None; -> its 4-tuple
+                densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
+                                                    opt.split_opacity_thresh, None, generator=gen,
+                                                    on_device=opt.densify_on_device)
             else:
-                raise ValueError("densify_rule must be '3dgs' or 'fsgs'")
+                raise ValueError("densify_rule must be '3dgs', 'fsgs' or 'dng'")
         if will_reset:
             m.reset_opacity()
             reset = True
@@ -1514,6 +1711,60 @@ class Trainer:
         finally:
             for k, v in saved.items():
                 setattr(be, k, v)
+
+    # -- DNGaussian's prunes between iterations (train_llff.py:206-213, 264-274): a re-layout each, so both are preceded by what
+    # the densification branch of train_iteration does before it touches the model
+    def _before_relayout(self, on_device, opt):
+        """-> on_device resolved (None: densify_on_device of `opt`, else of the options train_iteration last ran with, else off)"""
+        self.sync()
+        self.gather_optimizer_state()
+        if on_device is None:
+            on_device = getattr(opt if opt is not None else self.last_options, "densify_on_device", False)
+        return bool(on_device)
+
+    def prune_near_cameras(self, centers, near_range, on_device=None, opt=None):
+        """DNGaussian/train_llff.py:208-213: remove the Gaussians within `near_range` of any of the camera centres [K,3] (the
+        spiral path's) - near_camera_mask (one launch, no read-back; on a CPU model the reference's own torch statements) handed
+        to GaussianModelLite.prune_points.  on_device=None: densify_on_device of `opt`, or of the options train_iteration last
+        ran with; False when there are none.
+        Returns the number of rows removed."""
+        on_device = self._before_relayout(on_device, opt)
+        m = self.model
+        with torch.no_grad():
+            xyz = m.params["xyz"].detach()
+            centers = torch.as_tensor(centers, dtype=torch.float32).reshape(-1, 3).to(xyz.device)
+            if xyz.is_cuda:
+                from .dng_reg import near_camera_mask
+                mask = near_camera_mask(xyz, centers, near_range)
+            else:
+                mask = None
+                for c in centers:
+                    near = (xyz - c.repeat(xyz.shape[0], 1)).norm(dim=1, keepdim=True) < near_range
+                    mask = mask + near if mask is not None else near
+                mask = mask.squeeze(1)
+        return m.prune_points(mask, on_device=on_device)
+
+    def prune_unseen(self, camera_indices=None, on_device=None, opt=None):
+        """clean_views (DNGaussian/train_llff.py:264-274): remove the Gaussians no training view sees.  One forward-only render
+        per camera (default: all of the trainer's) as evaluate() makes them - plain forward under no_grad, own camera keys,
+        the backend's hints restored -, `radii > 0` ORed on the model's device with no read-back, then prune_points.
+        Returns the number of rows removed."""
+        on_device = self._before_relayout(on_device, opt)
+        m = self.model
+        idx = range(len(self.cameras)) if camera_indices is None else list(camera_indices)
+        be = self._backend()
+        saved = {k: getattr(be, k) for k in self._EVAL_KEEPS if be is not None and hasattr(be, k)}
+        seen = torch.zeros((m.P,), dtype=torch.bool, device=m.flat.device)
+        try:
+            with torch.no_grad():
+                for ci in idx:
+                    radii = render(self.cameras[ci], m, self.Rasterizer, self.Settings, self.bg, filter_as_indices=None,
+                                   clamp=False, camera_key=("trainer", self.uid, "eval", ci))["radii"]
+                    seen |= radii.reshape(-1) > 0
+        finally:
+            for k, v in saved.items():
+                setattr(be, k, v)
+        return m.prune_points(~seen, on_device=on_device)
 
     # The single-GPU fused step without the autograd engine: its graph is two custom nodes in a row (rasterizer, criterion) whose
     # gradients end inside gs_backward_step, so the step calls their forward / backward bodies itself (a stand-in context
