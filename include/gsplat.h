@@ -517,6 +517,24 @@ int gs_debug_blend_stats(const GsScratch* scratch, int32_t P, int32_t W, int32_t
  * binning): the lists of different tiles lie in point_list in no particular order, inside a tile the order is the reference's. */
 int gs_export_binning_region(const GsScratch* scratch, int32_t W, int32_t H, int64_t num_rendered, uint64_t* keys_sorted,
                              uint32_t* point_list, void* stream);
+/* Developer entries to the stable LSD radix sort of (u32 key, u32 value) pairs and to the one-workgroup scan behind the depth
+ * order, the region partition, the grid encoder's slot sort and the kNN's Morton sort (csrc/gs_binning.hip), run exactly as
+ * those callers run them.  tests/test_gpu_sort.py.  Every pointer is a device pointer.
+ * tmp: >= gs_debug_sort_tmp_bytes(n_bound) bytes, laid out as the callers' sort buffers; its contents on entry do not matter.
+ * The sort handles n = min(*n_dev, n_bound) pairs and orders them stably by the key's bits [0, end_bit) (8-bit passes, or with
+ * digit_bits = 9 one 9-bit pass: end_bit <= 9, else GS_E_SHAPE).
+ * depth_form = 0: keys / vals (n_bound words each) are copied into half `start_buf` of the ping-pong buffers and sorted.
+ * depth_form = 1: vals = NULL; the first pass reads `keys` in place (left untouched), value = index, keys 0xFFFFFFFF are
+ * dropped (n_bound > 16 384) or sorted to the tail (the one-workgroup form), *n_kept = number of the others.
+ * keys_out / vals_out: n_bound words each of the half the sort ends in - start_buf ^ (passes & 1), start_buf ^ 1 for the 9-bit
+ * form -; words at and beyond n are whatever `tmp` held.  digit_totals: NULL, or 512 words: after the 9-bit form the number of
+ * keys of every digit.  Returns the sort's own status. */
+size_t gs_debug_sort_tmp_bytes(int64_t n_bound);
+int gs_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, const uint32_t* n_dev, int64_t n_bound, int32_t end_bit,
+                        int32_t start_buf, int32_t digit_bits, int32_t depth_form, void* tmp, size_t tmp_bytes,
+                        uint32_t* keys_out, uint32_t* vals_out, uint32_t* n_kept, uint32_t* digit_totals, void* stream);
+/* In-place exclusive scan of sums[0, nb) by one workgroup; the total lands at sums[nb] (device, nb + 1 words). */
+int gs_debug_scan_sums(uint32_t* sums, int32_t nb, void* stream);
 
 /* ---- simple-knn ---- */
 /* out[i] = mean of the 3 smallest squared distances from point i to the other points.

@@ -930,4 +930,46 @@ int gs_export_binning_region(const GsScratch* sc, int32_t W, int32_t H, int64_t 
   return GS_OK;
 }
 
+/* Developer entries to the radix sort and the one-workgroup scan (csrc/gs_binning.hip) on their own: tests/test_gpu_sort.py. */
+size_t gs_debug_sort_tmp_bytes(int64_t n_bound) { return sort_bytes(n_bound > 0 ? (size_t)n_bound : 0); }
+
+int gs_debug_sort_pairs(const uint32_t* keys, const uint32_t* vals, const uint32_t* n_dev, int64_t n_bound, int32_t end_bit,
+                        int32_t start_buf, int32_t digit_bits, int32_t depth_form, void* tmp, size_t tmp_bytes, uint32_t* keys_out,
+                        uint32_t* vals_out, uint32_t* n_kept, uint32_t* digit_totals, void* stream) {
+  if (!keys || !n_dev || !tmp || !keys_out || !vals_out) return GS_E_NULL;
+  if (depth_form ? (vals != nullptr || !n_kept) : !vals) return GS_E_NULL;
+  if (n_bound <= 0 || n_bound > 0xFFFFFFFFll || end_bit < 1 || end_bit > 32 || (start_buf & ~1) || (digit_bits != 8 && digit_bits != 9))
+    return GS_E_SHAPE;
+  if (tmp_bytes < sort_bytes((size_t)n_bound)) return GS_E_SCRATCH;
+  hipStream_t s = (hipStream_t)stream;
+  const SortBufs b = sort_view(tmp, (size_t)n_bound);
+  const size_t bytes = 4 * (size_t)n_bound;
+  (void)hipGetLastError();
+  if (!depth_form) {
+    GS_HIP_CHECK(hipMemcpyAsync(b.keys[start_buf], keys, bytes, hipMemcpyDeviceToDevice, s));
+    GS_HIP_CHECK(hipMemcpyAsync(b.vals[start_buf], vals, bytes, hipMemcpyDeviceToDevice, s));
+  }
+  const int rc = launch_radix_sort(b, n_dev, n_bound, end_bit, start_buf, depth_form ? keys : nullptr, s, 0,
+                                   depth_form ? n_kept : nullptr, digit_bits);
+  if (rc) return rc;
+  // the half the callers read: one flip per pass (gs_encoding.hip reads half `passes & 1`, the depth and Morton sorts half 0 after
+  // their four), one flip for the 9-bit one-pass form (gs_tilebin.hip starts it in half 0 and reads half 1)
+  const int passes = (end_bit + RS_BITS - 1) / RS_BITS;
+  const int fin = digit_bits == 9 ? (start_buf ^ 1) : (start_buf ^ (passes & 1));
+  GS_HIP_CHECK(hipMemcpyAsync(keys_out, b.keys[fin], bytes, hipMemcpyDeviceToDevice, s));
+  GS_HIP_CHECK(hipMemcpyAsync(vals_out, b.vals[fin], bytes, hipMemcpyDeviceToDevice, s));
+  if (digit_totals) GS_HIP_CHECK(hipMemcpyAsync(digit_totals, b.scan_tmp, 4 * RS_RADIX_MAX, hipMemcpyDeviceToDevice, s));
+  return GS_OK;
+}
+
+int gs_debug_scan_sums(uint32_t* sums, int32_t nb, void* stream) {
+  if (!sums) return GS_E_NULL;
+  if (nb <= 0) return GS_E_SHAPE;
+  (void)hipGetLastError();
+  const int rc = launch_scan_sums(sums, nb, (hipStream_t)stream);
+  if (rc) return rc;
+  GS_LAUNCH_CHECK((hipStream_t)stream, 0);
+  return GS_OK;
+}
+
 }  // extern "C"

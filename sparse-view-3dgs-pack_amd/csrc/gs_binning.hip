@@ -186,7 +186,11 @@ __global__ void __launch_bounds__(NT) rs_scatter_kernel(const uint32_t* __restri
   const uint32_t n = min(*n_dev, n_bound);   // (see rs_hist_kernel)
   const uint32_t nblk = (n + RS_TILE - 1) / RS_TILE;   // (the table's row stride: see rs_hist_kernel)
   const uint32_t t0 = blockIdx.x * RS_TILE;
-  if (t0 >= n) return;
+  if (t0 >= n) {
+    // no key at all: the first workgroup still owes the count of the kept keys - the later passes read it as THEIR count
+    if (n_kept && blockIdx.x == 0 && threadIdx.x == 0) *n_kept = 0;
+    return;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
 #pragma unroll
   for (int k = tid; k < NW * RADIX; k += NT) (&s_hist[0][0])[k] = 0;
@@ -318,15 +322,16 @@ int launch_bin_prepare(const GeomView& g, int64_t capacity, uint2* ranges, int T
 #define RS_SMALL_ITEMS 16
 #define RS_SMALL_MAX (1024 * RS_SMALL_ITEMS)
 __global__ void __launch_bounds__(1024) rs_small_sort_kernel(const uint32_t* __restrict__ kin, const uint32_t* n_dev,
-                                                             uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                             int end_bit, uint32_t* __restrict__ n_kept) {
+                                                             uint32_t n_bound, uint32_t* __restrict__ kout,
+                                                             uint32_t* __restrict__ vout, int end_bit,
+                                                             uint32_t* __restrict__ n_kept) {
   constexpr int NT = 1024, NW = NT / 64, ITEMS = RS_SMALL_ITEMS;
   __shared__ uint32_t s_hist[NW][RS_RADIX];
   __shared__ uint32_t s_key[RS_SMALL_MAX];
   __shared__ uint32_t s_val[RS_SMALL_MAX];
   __shared__ uint32_t s_wtot[RS_RADIX / 64];
   __shared__ uint32_t s_kept;
-  const uint32_t n = min(*n_dev, (uint32_t)RS_SMALL_MAX);
+  const uint32_t n = min(*n_dev, min(n_bound, (uint32_t)RS_SMALL_MAX));   // (see rs_hist_kernel: kin / kout / vout hold n_bound words)
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (tid == 0) s_kept = 0;
   __syncthreads();
@@ -428,8 +433,8 @@ int launch_radix_sort(const SortBufs& b, const uint32_t* n_dev, int64_t n_bound,
   if (first_keys != nullptr && n_bound <= RS_SMALL_MAX) {
     const int passes = (end_bit + RS_BITS - 1) / RS_BITS;
     const int fin = start_buf ^ (passes & 1);  // where the pass-by-pass form would leave the result
-    hipLaunchKernelGGL(rs_small_sort_kernel, dim3(1), dim3(1024), 0, s, first_keys, n_dev, b.keys[fin], b.vals[fin], end_bit,
-                       n_kept);
+    hipLaunchKernelGGL(rs_small_sort_kernel, dim3(1), dim3(1024), 0, s, first_keys, n_dev, (uint32_t)n_bound, b.keys[fin],
+                       b.vals[fin], end_bit, n_kept);
     GS_LAUNCH_CHECK(s, debug);
     return 0;
   }

@@ -169,6 +169,9 @@ PROTOTYPES = {
     "forward_bin": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P]),
     "export_binning_region": (C.c_int, [C.POINTER(GsScratch), _I32, _I32, _I64, _P, _P, _P]),
     "debug_blend_stats": (C.c_int, [C.POINTER(GsScratch), _I32, _I32, _I32, _P, _P]),
+    "debug_sort_tmp_bytes": (_SZ, [_I64]),
+    "debug_sort_pairs": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _P, _P, _P]),
+    "debug_scan_sums": (C.c_int, [_P, _I32, _P]),
     "tile_depth_limit_floats": (C.c_size_t, [_I32, _I32]),
     "knn_tmp_bytes": (_SZ, [_I32]),
     "knn_mean_dist2": (C.c_int, [_P, _I32, _P, _P, _SZ, _P]),
@@ -310,7 +313,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_unin
                "depth_forward", "depth_backward",
                # the reference-API optimizer's one-launch step (restated in numpy: tests/sparse_adam_reference.py) and the backward
                # for the model's split SH rows - a memory layout of the product, compared against gs_backward's slices on the GPU
-               "adam_step_tensors", "backward_split")
+               "adam_step_tensors", "backward_split",
+               # the radix sort and the one-workgroup scan on their own: restated in numpy (tests/sort_cases.py)
+               "debug_sort_tmp_bytes", "debug_sort_pairs", "debug_scan_sums")
 
 ERRORS = {-1: "GS_E_NULL", -2: "GS_E_SHAPE", -3: "GS_E_SCRATCH", -4: "GS_E_OVERFLOW", -5: "GS_E_UNSUPPORTED"}
 

@@ -55,6 +55,8 @@ SHAPES = [
     ("trained", 700, 48, 40, 1),        # one region row; fewer Gaussians than the one-workgroup sort holds
     ("trained", 20000, 2100, 80, 1),    # 132 x 5 tiles: more than 256 regions would need two partition passes... (33 x 2 here)
     ("trained", 20000, 4100, 1100, 1),  # 257 x 69 tiles = 65 x 18 = 1170 regions: two partition passes
+    ("trained", 16384, 250, 130, 1),    # the most Gaussians the one-workgroup depth sort takes ...
+    ("trained", 16385, 250, 130, 1),    # ... and the fewest the multi-pass sort does (csrc/gs_binning.hip, tests/test_gpu_sort.py)
     ("huge", 200, 3840, 2160, 0),       # splats that cover a 4K image: up to 2 040 entries per Gaussian, 256 of them per workgroup
 ]
 
@@ -96,6 +98,33 @@ def test_culled_lists_do_not_depend_on_the_entry_enumeration(hip, kind, P, W, H,
     assert bool((keys[1:] >= keys[:-1]).all())
     ca, ka = canonical_lists(a)
     assert int(ca.sum()) == a["num_rendered"] and np.array_equal(np.sort(ka), np.unique(ka))  # no duplicate pairs
+
+
+def test_three_survivors_of_twenty_thousand(hip, oracle):
+    """20 000 Gaussians of which all but three lie behind the camera: the first pass of the multi-pass depth sort drops 19 997
+    keys (four of its five tiles keep nothing) and the later passes, the entry emission and the partition run on three."""
+    from test_gpu_raster_parity import compare_forward
+    P, W, H = 20000, 250, 130
+    sc = synthetic.trained_like(P, seed=5, sh_degree=1)
+    cam = synthetic.orbit_cameras(W, H)[2]
+    wv = cam.world_view_transform.double()
+    xyz = sc["means3D"].double()
+    z = xyz @ wv[:3, 2] + wv[3, 2]
+    assert float(z.min()) > 0.5, "the cloud lies in front of the camera"
+    keep = torch.argsort(xyz.norm(dim=1))[:3]            # the three nearest the point the camera looks at
+    behind = xyz - 2.0 * z[:, None] * wv[:3, 2][None]    # mirrored at the camera's plane: view depth -z
+    behind[keep] = xyz[keep]
+    sc["means3D"] = behind.float()
+    bg = torch.tensor([0.1, 0.2, 0.3])
+    hip.tile_cull = False
+    h = forward_state(hip, sc, cam, DEV, bg, False)
+    o = forward_state(oracle.backend, sc, cam, torch.device("cpu"), bg, False)
+    assert torch.equal(torch.nonzero(o["radii"] > 0).flatten(), torch.sort(keep).values)
+    assert h["num_rendered"] == o["num_rendered"] >= 3
+    for k in ("radii", "tiles_touched", "point_offsets", "ranges", "point_list", "keys_sorted"):
+        assert torch.equal(h[k], o[k]), k
+    assert set(h["point_list"].tolist()) == set(keep.tolist())
+    compare_forward(h, o, "three_survivors")   # colour (and the rest of the forward state) at the parity suite's bars
 
 
 def test_too_small_a_capacity_is_detected_and_the_view_rendered_again(hip):
