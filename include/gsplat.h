@@ -104,7 +104,8 @@ typedef struct GsGaussians {
                                   takes them.  1: they are the model's RAW rows (gaussian_model.py:60-78) and the kernels
                                   apply sigmoid / exp / F.normalize on the fly, with gs_activations_fwd's arithmetic bit for
                                   bit - so the activated copies are never written nor read.  Honoured by
-                                  gs_forward_geometry and gs_backward_step only (the plain backward returns gradients
+                                  gs_forward_geometry (hence by every forward render behind it, gs_forward_render_fsgs
+                                  included) and by gs_backward_step / _x / _fsgs only (the plain backwards return gradients
                                   with respect to the activated values: GS_E_UNSUPPORTED with this flag) */
   const float* extra_gain;     /* with raw_activations and extra_channel: device scalar; the blended 4th channel is then
                                   sigmoid(extra_channel[i]) * clamp(*extra_gain, 0.1, 10) - the multispectral model's raw NIR
@@ -440,6 +441,20 @@ int gs_backward_step_x(const GsView* view, const GsGaussians* g, const int32_t* 
                        const GsScratch* scratch, int64_t num_rendered, const float* dL_dcolor,
                        const float* dL_dinvdepth, const float* dL_dextra_img, const GsStepState* st,
                        void* workspace, size_t workspace_bytes, void* stream);
+/* gs_backward_step behind gs_forward_render_fsgs (the FSGS / DNGaussian rasterizer generation; FSGS/train.py:133-176 is one
+ * camera per optimizer step, so every gradient is final after this view): dL_ddepth / dL_dalpha [H,W] are the image
+ * gradients of that generation's depth and alpha outputs, as gs_backward_fsgs takes them.  Same per-Gaussian kernel, same
+ * element arithmetic: given the same blend sums the call leaves the bits that gs_backward_fsgs + gs_activations_bwd +
+ * gs_densify_stats + gs_adam_step leave.  Both forms of GsStepState are served - Adam inside (m / v) and gradients out
+ * (grad_out, with split SH rows through shs_rest / grad_out_rest as gs_backward_step serves them) - and so are
+ * GsGaussians.raw_activations, rows_override, rows_clean, reached_split, dormant, sparse, coef_dev and fail_flag.
+ * Status codes, no launch: GS_E_NULL for a NULL dL_ddepth, dL_dalpha or st; GS_E_UNSUPPORTED for view->antialiasing, for a
+ * 4th channel (g->extra_channel or st->extra: this generation has none) and for st->phase != 0 (no two-phase form: do not
+ * pair it with gs_step_uninstanced); everything gs_backward_step refuses (GsStepState's rules above). */
+int gs_backward_step_fsgs(const GsView* view, const GsGaussians* g, const int32_t* radii,
+                          const GsScratch* scratch, int64_t num_rendered, const float* dL_dcolor,
+                          const float* dL_ddepth, const float* dL_dalpha, const GsStepState* st,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* The part of gs_backward_step that does not wait for the loss: a Gaussian that emitted no instance in this view
  * (tiles_touched == 0: off screen, culled, or cut by the depth limits - four fifths of them on depth-limited lists) has

@@ -548,6 +548,22 @@ int gs_backward_step_x(const GsView* v, const GsGaussians* g, const int32_t* rad
                        stream, st);
 }
 
+// gs_backward_step behind gs_forward_render_fsgs.  The per-Gaussian step kernel does not know the rasterizer generation: the
+// mode enters the blend backward (GS_BWD_WAVE(true, true, true)) and the depth part of dmean in chain_from_row
+// (has_invdepth == 2); the statistics read the mean2D slots of the record, the reached flags are written by every forward
+// instantiation, and the rows are cleaned by the chain kernel whatever the mode.
+int gs_backward_step_fsgs(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc, int64_t num_rendered,
+                          const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, const GsStepState* st,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (!st || !dL_ddepth || !dL_dalpha) return GS_E_NULL;
+  if (v && v->antialiasing) return GS_E_UNSUPPORTED;  // that rasterizer generation has no anti-aliasing
+  if ((g && g->extra_channel) || st->extra) return GS_E_UNSUPPORTED;  // ... and no 4th channel
+  if (st->phase != 0) return GS_E_UNSUPPORTED;  // one launch steps every Gaussian: no two-phase form for this generation
+  const GsGrads none = {};
+  return backward_impl(v, g, radii, sc, num_rendered, dL_dcolor, dL_ddepth, dL_dalpha, 1, &none, workspace, workspace_bytes,
+                       stream, st);
+}
+
 int gs_step_uninstanced(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc, const GsStepState* st,
                         void* stream) {
   int rc = check_args(v, g);

@@ -33,3 +33,11 @@ def rasterize_gaussians_backward(*args, opacities=None):
 
 def mark_visible(*args):
     return hip_backend().mark_visible(*args)
+
+
+def __getattr__(name):
+    # `backend`: the RasterBackend behind this module, for callers that arm its one-shot requests (the fused train step of
+    # gsplat_amd.trainer.TrainerFSGS); resolved on first use, like every call above
+    if name == "backend":
+        return hip_backend()
+    raise AttributeError(name)

@@ -23,6 +23,22 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
                                      cov3Ds_precomp, raster_settings)
 
 
+_ONES = {}   # id(confidence tensor) -> (weak reference, version, verdict): one read-back per tensor, not per step
+
+
+def _all_ones(c):
+    """Is the confidence tensor all ones?  Asked only when a fused train step is armed (its backward cannot scale by it)."""
+    import weakref
+    ent = _ONES.get(id(c))
+    if ent is not None and ent[0]() is c and ent[1] == c._version:
+        return ent[2]
+    ok = bool((c == 1).all())
+    if len(_ONES) > 64:
+        _ONES.clear()
+    _ONES[id(c)] = (weakref.ref(c), c._version, ok)
+    return ok
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     _impl = _C  # swapped by the test-suite to run the same plumbing on another implementation of the C ABI
 
@@ -30,6 +46,12 @@ class _RasterizeGaussians(torch.autograd.Function):
     def forward(cls, ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
         rs = raster_settings
+        be = getattr(cls._impl, "backend", None)
+        if be is not None and getattr(be, "fused_step", None) is not None and not _all_ones(rs.confidence):
+            # the backward of an armed fused train step returns no gradients: the fused Adam has no place to scale them by
+            be.fused_step, be.raw_activations, be.sh_rest = None, False, None
+            raise RuntimeError("a confidence that is not all ones is closed to the fused train step of the FSGS rasterizer "
+                               "generation (pipe.use_confidence is False in FSGS): take the un-fused step")
         args = (rs.bg, means3D, colors_precomp, opacities, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                 rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
                 rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)

@@ -155,6 +155,8 @@ PROTOTYPES = {
                                 C.POINTER(GsStepState), _P, _SZ, _P]),
     "backward_step_x": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, _P,
                                   C.POINTER(GsStepState), _P, _SZ, _P]),
+    "backward_step_fsgs": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, _P,
+                                     C.POINTER(GsStepState), _P, _SZ, _P]),
     "backward_from_rows": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _P, _I32,
                                      C.POINTER(GsGrads), _P, _SZ, _P]),
     "mark_visible": (C.c_int, [_I32, _P, _P, _P, _P, _P]),
@@ -279,7 +281,7 @@ PROTOTYPES = {
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
 # (and the fused 4-channel pass is a product-side fusion of two reference passes: its parity target is the
 # reference's two 3-channel passes, so the checker does not need it)
-DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "step_uninstanced", "export_tile_order", "export_tile_stop_depth", "forward_status", "forward_bin", "export_binning_region", "region_coop", "debug_blend_stats", "adam_step_gated", "tile_depth_limit_floats", "profile_enable", "profile_only", "profile_reset", "profile_stage_count", "profile_stage_name", "profile_read",
+DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_step_fsgs", "step_uninstanced", "export_tile_order", "export_tile_stop_depth", "forward_status", "forward_bin", "export_binning_region", "region_coop", "debug_blend_stats", "adam_step_gated", "tile_depth_limit_floats", "profile_enable", "profile_only", "profile_reset", "profile_stage_count", "profile_stage_name", "profile_read",
                "forward_render_x", "backward_x", "forward_tile_order",
                # the image stage (exposure, clamp, alpha mask) and the exposures' Adam: the oracle restates them in torch
                "image_stage_partials_count", "image_stage_fwd", "image_stage_bwd", "exposure_adam",

@@ -153,6 +153,7 @@ class RasterBackend:
         # parity probes: keep the backward workspace (the per-Gaussian 16-slot float64 gradient rows of the blend backward)
         self.keep_workspace = False
         self.last_workspace = None
+        self._zero_images = {}    # (device, H, W) -> [1,H,W] zeros (_zero_image)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self, device):
@@ -549,7 +550,9 @@ class RasterBackend:
         extra [P] (not part of the reference's signature): a 4th per-Gaussian channel blended in the same
         pass (gs_forward_render_x); the tuple then ends with its image [1,H,W].
         fsgs=True: the older generation of FSGS / DNGaussian (gs_forward_render_fsgs): the "invdepth" slot of the
-        tuple holds depth = sum depth alpha T and the tuple ends with alpha = sum alpha T, both [1,H,W]."""
+        tuple holds depth = sum depth alpha T and the tuple ends with alpha = sum alpha T, both [1,H,W].  It takes the
+        one-shot `raw_activations` like the newer generation (the geometry phase is shared); with a `fused_step` armed its
+        backward is gs_backward_step_fsgs, and depth limits and the capture-safe forward are refused."""
         if fsgs and (extra is not None or antialiasing):
             raise RuntimeError("the FSGS rasterizer generation has neither anti-aliasing nor a 4th channel")
         if means3D.ndim != 2 or means3D.shape[1] != 3:
@@ -584,8 +587,16 @@ class RasterBackend:
         if sh_rest is not None and not raw and (not sh_activated or fsgs or extra is not None):
             raise RuntimeError("split SH rows are served with raw activations only (gsplat_amd.render_raw), or on activated "
                                "values by the plain rasterizer call of gsplat_amd.accel")
-        if raw and fsgs:
-            raise RuntimeError("raw activations do not serve the FSGS rasterizer generation")
+        if fsgs and self.fused_step is not None:
+            # the fused train step of the FSGS generation (gs_backward_step_fsgs) is the one-launch eager form only
+            closed = None
+            if self.static_capacity is not None:
+                closed = "the capture-safe forward (GraphedStep, hipGraph replay) is"
+            elif self.depth_limit_request is not None or self.depth_limit_on or self.camera_key_limits:
+                closed = "depth-limited lists are"
+            if closed is not None:   # (nothing stays armed behind the refusal)
+                self.fused_step, self.depth_limit_request, self.camera_key, self.camera_key_limits = None, None, None, False
+                raise RuntimeError("%s closed to the fused train step of the FSGS rasterizer generation" % closed)
         if (extra_gain is not None) != (raw and extra is not None):
             raise RuntimeError("extra_gain goes with a RAW 4th channel (raw activations), and only with it")
         if device.type == "cuda":
@@ -944,7 +955,8 @@ class RasterBackend:
 
         Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
         dL_drotations) (+ dL_dextra [P] when the forward blended a 4th channel).
-        fsgs=True: dL_dout_invdepth is the depth image gradient and dL_dout_extra the alpha image gradient.
+        fsgs=True: dL_dout_invdepth is the depth image gradient and dL_dout_extra the alpha image gradient; with an armed
+        fused_step the call is gs_backward_step_fsgs (one launch for every Gaussian, no side launch) and returns eight Nones.
         raw=True: the forward read raw rows (GsGaussians.raw_activations) - said by a caller whose forward may not be the last
         one; the last forward's own record says it for its backward."""
         self._check_device(means3D)
@@ -968,8 +980,8 @@ class RasterBackend:
         if raw and (step is None or P == 0):
             raise RuntimeError("a forward on raw activations must be followed by the fused train-step backward")
         fused = step is not None and P != 0
-        if fused and fsgs:
-            raise RuntimeError("the fused train-step backward does not serve the FSGS rasterizer generation")
+        if fused and fsgs and not hasattr(self.api, "_backward_step_fsgs"):
+            raise RuntimeError("this library has no fused train-step backward for the FSGS rasterizer generation")
         dL_dout_color, dL_dout_invdepth = _prep(dL_dout_color, device), _prep(dL_dout_invdepth, device)
         # dL_dout_extra from here on: the 4th channel's image gradient (zeros when not given); with fsgs the alpha image's;
         # else None
@@ -989,14 +1001,57 @@ class RasterBackend:
         args = (view, g, radii.contiguous(), geomBuffer, binningBuffer, imgBuffer, P, W, H, R, dL_dout_color, dL_dout_invdepth,
                 dL_dout_extra)
         if fused:
-            return self._backward_step(step, f, *args)
+            return self._backward_step(step, f, *args, fsgs=fsgs)
         return self._backward_grads(arena, fsgs, *args)
 
+    def _zero_image(self, device, H, W):
+        """One [1,H,W] image of zeros per device and size, never written: the cotangent of an output nobody differentiated."""
+        key = (device.index, H, W)
+        z = self._zero_images.get(key)
+        if z is None:
+            if len(self._zero_images) > 8:
+                self._zero_images.clear()
+            z = self._zero_images[key] = torch.zeros((1, H, W), dtype=torch.float32, device=device)
+        return z
+
+    def _backward_step_fsgs(self, step, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color, dL_ddepth, dL_dalpha):
+        """gs_backward_step_fsgs: the fused train-step backward behind gs_forward_render_fsgs.  One launch steps every
+        Gaussian: the side launch of the two-phase step is closed to this generation."""
+        device = radii.device
+        if step.phase != 0 or step.phase1_done:
+            raise RuntimeError("the two-phase step (side launch of gs_step_uninstanced) is closed to the FSGS rasterizer "
+                               "generation")
+        if step.extra:
+            raise RuntimeError("the FSGS rasterizer generation has no 4th channel to step")
+        _, _, _, wsb = self.scratch_bytes(P, W, H, R)
+        ws = self._rows_workspace(step, device, wsb)
+        s = self._scratch(geom, img, binning, self._capacity_for(binning, P, W, H, R))
+        last = self._last
+        if last is not None:
+            last.step = last.radii = last.img = last.done = None
+        step.reached_split = int(self.REACHED_SPLIT)
+        dL_ddepth, dL_dalpha = _prep(dL_ddepth, device), _prep(dL_dalpha, device)
+        zeros = self._zero_image(device, H, W) if dL_ddepth is None or dL_dalpha is None else None
+        try:
+            self.api.call("backward_step_fsgs", C.byref(view), C.byref(g), radii.data_ptr(), C.byref(s), int(R),
+                          dL_dout_color.data_ptr(), (dL_ddepth if dL_ddepth is not None else zeros).data_ptr(),
+                          (dL_dalpha if dL_dalpha is not None else zeros).data_ptr(), C.byref(step), _ptr(ws), ws.numel(),
+                          self._stream(device))
+        except Exception:
+            self.rows_epoch += 1
+            raise
+        if step.rows_clean:
+            self._rows_ws[(device.index, wsb)][1] = True
+        return (None,) * 8
+
     def _backward_step(self, step, f, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color, dL_dout_invdepth,
-                       dL_dout_extra):
+                       dL_dout_extra, fsgs=False):
         """gs_backward_step[_x] for the train step armed as `step` (backward, activation backward, view statistics and Adam
         in one per-Gaussian kernel - or its gradients-out form); `f`: the forward's record when it is the last one.
         Returns no gradients at all."""
+        if fsgs:
+            return self._backward_step_fsgs(step, view, g, radii, geom, binning, img, P, W, H, R, dL_dout_color,
+                                            dL_dout_invdepth, dL_dout_extra)
         device = radii.device
         _, _, _, wsb = self.scratch_bytes(P, W, H, R)
         ws = self._rows_workspace(step, device, wsb)

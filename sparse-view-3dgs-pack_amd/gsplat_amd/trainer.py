@@ -2440,6 +2440,257 @@ class TrainerNIR(Trainer):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# FSGS: the train loop of FSGS/train.py on the FSGS rasterizer generation
+# ----------------------------------------------------------------------------------------------------------------
+class FsgsOptions(TrainOptions):
+    """FSGS/arguments/__init__.py:76-99 (OptimizationParams) over the fields of TrainOptions."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.iterations = 10_000
+        self.position_lr_max_steps = 10_000
+        self.densify_until_iter = 10_000
+        self.densify_grad_threshold = 0.0005
+        self.min_opacity = 0.005           # prune_threshold
+        self.prune_from_iter = 500
+        self.dist_thres = 10.0
+        self.start_sample_pseudo = 2000
+        self.end_sample_pseudo = 9500
+        self.sample_pseudo_interval = 10
+        self.depth_weight = 0.05
+        self.depth_pseudo_weight = 0.5
+        self.late_depth_weight = 0.001     # train.py:111-112: what depth_weight becomes beyond end_sample_pseudo
+        self.opacity_reset_value = 0.05    # scene/gaussian_model.py:231
+        self.sh_increase_interval = 500    # train.py:82
+        self.densify_rule = "fsgs"
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError("unknown option %s" % k)
+            setattr(self, k, v)
+
+
+def render_fsgs(viewpoint_camera, pc, Rasterizer, Settings, bg_color, confidence, scaling_modifier=1.0, debug=False,
+                raw_activations=False, torch_activations=False):
+    """= render() of FSGS/gaussian_renderer/__init__.py:20-132 (SH evaluated by the rasterizer, scale + rotation given, no
+    trainable background): {render, viewspace_points, visibility_filter, radii, depth, alpha}; the image is NOT clamped.
+    raw_activations: the rasterizer gets the RAW scaling / rotation / opacity rows (the caller has told the backend) - the
+    fused train step's form; the view-space leaf is then never filled.  visibility_filter is None: the statistics read radii.
+    torch_activations: exp / normalize / sigmoid as torch ops instead of the model's fused activation node, whose backward
+    WRITES the three gradients into the model's flat gradient buffer - right for one render per backward, wrong for two."""
+    if raw_activations:
+        scales, rotations, opacities = pc.params["scaling"], pc.params["rotation"], pc.params["opacity"]
+        screenspace_points = torch.empty_like(pc.get_xyz).requires_grad_(True)
+    else:
+        act = None if torch_activations else pc.fused_activations()
+        scales, rotations, opacities = act if act is not None else (pc.get_scaling, pc.get_rotation, pc.get_opacity)
+        screenspace_points = torch.zeros_like(pc.get_xyz, dtype=pc.get_xyz.dtype, requires_grad=True) + 0
+        try:
+            screenspace_points.retain_grad()
+        except Exception:
+            pass
+    rs = Settings(
+        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5), bg=bg_color,
+        scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
+        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
+        campos=viewpoint_camera.camera_center, prefiltered=False, debug=debug, confidence=confidence)
+    rendered_image, radii, depth, alpha = Rasterizer(raster_settings=rs)(
+        means3D=pc.get_xyz, means2D=screenspace_points, shs=pc.get_features, colors_precomp=None, opacities=opacities,
+        scales=scales, rotations=rotations, cov3D_precomp=None)
+    return {"render": rendered_image, "viewspace_points": screenspace_points, "visibility_filter": None, "radii": radii,
+            "depth": depth, "alpha": alpha}
+
+
+class TrainerFSGS(Trainer):
+    """The loop of FSGS/train.py:81-176 on the FSGS rasterizer generation (dgr_fsgs: colour, depth and alpha outputs), one GPU.
+
+    A plain iteration - one camera, one optimizer step - takes the fused train step: raw parameter rows into
+    gs_forward_render_fsgs, FsgsCriterion as one node on the un-clamped image and the depth image, gs_backward_step_fsgs
+    (backward, activation backward, view statistics and Adam in the per-Gaussian kernel).  A pseudo-view iteration
+    (train.py:116-131) renders a second camera before the one backward: two views feed one Adam step, so it takes the
+    UN-fused path on purpose - both backwards accumulate into the model's gradients, then FlatAdam.step.  A densifying
+    iteration is un-fused too (no optimizer step, as in Trainer).
+
+    midas_depths: per training camera the monocular depth map [H,W] (viewpoint_cam.depth_image).
+    pseudo_cameras + depth_estimator: the pseudo leg.  depth_estimator(rendered image [3,H,W]) -> depth [H,W] stands for
+    FSGS's estimate_depth(..., mode='train') (MiDaS, which this package does not ship); its result may carry gradient.
+    Without both the pseudo leg is OFF - a divergence from the reference, whose loop always samples pseudo views.
+    pearson / pseudo_pearson: the depth terms of the un-fused path as callables (rendered, midas) -> loss, for models that do
+    not live on the GPU (gsplat_amd.pearson has no CPU path); default: gsplat_amd.pearson's two functions.
+    Closed to this trainer: world_size > 1, with_nir models, trained exposure, alpha masks, depth limits, "sparse_adam",
+    the two-phase side launch and GraphedStep."""
+
+    def __init__(self, model, cameras, gt_images, midas_depths, criterion, bg, Rasterizer=None, Settings=None,
+                 pseudo_cameras=None, depth_estimator=None, pearson=None, pseudo_pearson=None, depth_weight=0.05,
+                 opacity_lr=0.05, depth_limit=None, **kw):
+        if Rasterizer is None or Settings is None:
+            import dgr_fsgs
+            Rasterizer = Rasterizer or dgr_fsgs.GaussianRasterizer
+            Settings = Settings or dgr_fsgs.GaussianRasterizationSettings
+        closed = None
+        if kw.get("world_size", 1) > 1:
+            closed = "data parallelism (world_size > 1)"
+        elif getattr(model, "with_nir", False):
+            closed = "a multispectral (with_nir) model"
+        elif getattr(model, "exposure", None) is not None:
+            closed = "a trained exposure"
+        elif kw.get("alpha_masks") is not None:
+            closed = "alpha masks"
+        elif depth_limit is not None:
+            closed = "depth-limited lists (depth_limit)"
+        elif kw.get("optimizer_type", "default") == "sparse_adam":
+            closed = 'optimizer_type = "sparse_adam"'
+        if closed is not None:
+            raise RuntimeError("TrainerFSGS: %s is closed to the FSGS rasterizer generation's trainer" % closed)
+        super().__init__(model, cameras, gt_images, criterion, Rasterizer, Settings, bg, **kw)
+        if len(midas_depths) != len(cameras):
+            raise ValueError("TrainerFSGS: one MiDaS depth map per training camera")
+        self.midas = midas_depths
+        self.pseudo_cameras = pseudo_cameras
+        self.depth_estimator = depth_estimator
+        self.pearson, self.pseudo_pearson = pearson, pseudo_pearson
+        self.depth_weight = depth_weight      # args.depth_weight: train_iteration lowers it beyond end_sample_pseudo
+        self._weight_from_options = False
+        self._pseudo_stack = []
+        self._conf = None
+        # FSGS/arguments/__init__.py:82: opacity_lr 0.05 (the model's default is LGDWT-GS's 0.025)
+        opt = model.optimizer
+        if isinstance(opt, FlatAdam):
+            opt.lr["opacity"] = opacity_lr
+        else:
+            for g in opt.opt.param_groups:
+                if g["name"] == "opacity":
+                    g["lr"] = opacity_lr
+
+    @property
+    def depth_limit(self):
+        return None
+
+    @depth_limit.setter
+    def depth_limit(self, v):
+        if v is not None:
+            raise RuntimeError("TrainerFSGS: depth-limited lists (depth_limit) are closed to the FSGS rasterizer generation's "
+                               "trainer")
+
+    def pseudo_on(self):
+        return bool(self.pseudo_cameras) and self.depth_estimator is not None
+
+    def _confidence(self):
+        """torch.ones_like(pc.confidence), gaussian_renderer/__init__.py:42 (pipe.use_confidence is False): one tensor per size"""
+        m = self.model
+        c = self._conf
+        if c is None or c.shape[0] != m.P or c.device != m.flat.device:
+            c = self._conf = torch.ones((m.P, 1), dtype=torch.float32, device=m.flat.device)
+        return c
+
+    def _fused_step_ok(self, backend, optimizer_step):
+        return (getattr(self.criterion, "fused", False) and super()._fused_step_ok(backend, optimizer_step)
+                and hasattr(backend.api, "_backward_step_fsgs"))
+
+    def _fused_dp_ok(self, backend, optimizer_step):
+        return False
+
+    def _render_camera(self, cam, raw, two_views=False):
+        return render_fsgs(cam, self.model, self.Rasterizer, self.Settings, self.bg, self._confidence(), raw_activations=raw,
+                           torch_activations=two_views)
+
+    def _render_view(self, ci, fused, raw):
+        return self._render_camera(self.cameras[ci], raw)
+
+    def _loss(self, pkg, ci, fused):
+        """FSGS/train.py:94-109 for training camera ci -> (loss, parts); no backward"""
+        if fused:
+            return self.criterion.fused_call(pkg["render"], pkg["depth"], self.gts[ci], self.midas[ci], self.depth_weight)
+        return self.criterion(pkg["render"], pkg["depth"], self.gts[ci], self.midas[ci], self.depth_weight, pearson=self.pearson)
+
+    def _criterion_backward(self, pkg, ci, mask, fused, side_launch):
+        loss, parts = self._loss(pkg, ci, fused)
+        self._arm_side_launch(None)   # (no side launch for this generation: nothing to issue from inside the criterion's backward)
+        if fused:
+            torch.autograd.backward(loss, self.criterion.ops.unit_grad(loss.device))
+        else:
+            loss.backward()
+        return loss, parts
+
+    def _step_pseudo(self, ci, pi, optimizer_step, skip, pseudo_scale):
+        """An iteration with the pseudo leg (train.py:116-134): the training view's loss, the pseudo view's depth term, ONE
+        backward through both renders, then the un-fused tail - statistics from the training view only.
+        -> (loss, whether the pseudo term entered it)"""
+        m = self.model
+        m.zero_grad()
+        fused = getattr(self.criterion, "fused", False)
+        # (two renders under one backward: the activations are torch ops, whose gradients autograd ADDS up)
+        pkg = self._render_camera(self.cameras[ci], False, two_views=True)
+        loss, parts = self._loss(pkg, ci, fused)
+        pkg2 = self._render_camera(self.pseudo_cameras[pi], False, two_views=True)
+        midas2 = self.depth_estimator(pkg2["render"])
+        pp = self.pseudo_pearson
+        if pp is None:
+            from .pearson import pseudo_depth_pearson_loss as pp
+        term = pp(pkg2["depth"][0].reshape(-1, 1), midas2.reshape(-1, 1)).mean()
+        entered = not bool(torch.isnan(term).sum())   # (train.py:129: the loop's one host read, on these iterations only)
+        if entered:
+            loss = loss + pseudo_scale * term
+        loss.backward()
+        self._unfused_tail(pkg, pkg["radii"], optimizer_step, skip)
+        self.last = dict(loss=loss.detach(), radii=pkg["radii"], parts=dict(parts, pseudo=term.detach()), path="unfused")
+        return loss.detach(), entered
+
+    def _draw_pseudo(self):
+        """train.py:117-119: pseudo cameras are drawn without replacement from their own stack, by the loop's one RNG"""
+        if not self._pseudo_stack:
+            self._pseudo_stack = list(range(len(self.pseudo_cameras)))
+        return self._pseudo_stack.pop(self._rng.randint(0, len(self._pseudo_stack) - 1))
+
+    def train_iteration(self, iteration, opt):
+        """One iteration (1-based) of FSGS/train.py:81-176, in its order: SH ramp, camera draw, loss (depth_weight is lowered
+        AFTER the loss of the first iteration beyond end_sample_pseudo is formed), the pseudo leg on its schedule, backward,
+        statistics from the training view, FSGS's densification (size_threshold None), the optimizer step (none on a
+        densifying iteration, as in Trainer), THEN the learning rate of this iteration - so the step of iteration k uses
+        the rate of k - 1 and the first the initial one - and the opacity reset, after the step, no group skipped.
+        Returns dict(loss, camera, sh_degree, xyz_lr (the rate the step used), depth_weight (the weight the loss used),
+        stepped, densified (FSGS's 4-tuple or None), reset, pseudo (the pseudo term entered the loss), path, P).
+        (The statistics are taken on every iteration, not only below densify_until_iter: nothing reads them afterwards.)"""
+        self.last_options = opt
+        m = self.model
+        if not self._weight_from_options:
+            self.depth_weight, self._weight_from_options = opt.depth_weight, True
+        if iteration % opt.sh_increase_interval == 0:
+            m.oneupSHdegree()
+        ci = self.draw_cameras(opt.seed)
+        pseudo = (self.pseudo_on() and iteration % opt.sample_pseudo_interval == 0
+                  and opt.start_sample_pseudo < iteration < opt.end_sample_pseudo)
+        will_densify = (iteration < opt.densify_until_iter and iteration > opt.densify_from_iter
+                        and iteration % opt.densification_interval == 0)
+        do_step = iteration < opt.iterations and not will_densify
+        o = m.optimizer
+        lr_used = o.lr["xyz"] if isinstance(o, FlatAdam) else next(g["lr"] for g in o.opt.param_groups if g["name"] == "xyz")
+        weight_used = self.depth_weight
+        entered = False
+        if pseudo:
+            pi = self._draw_pseudo()
+            scale = min((iteration - opt.start_sample_pseudo) / 500., 1) * opt.depth_pseudo_weight
+            loss, entered = self._step_pseudo(ci, pi, do_step, (), scale)
+        else:
+            loss = self._step_camera(ci, do_step, ())
+        if iteration > opt.end_sample_pseudo:   # train.py:111-112
+            self.depth_weight = opt.late_depth_weight
+        densified = None
+        if will_densify:
+            gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
+            densified = m.densify_and_prune_fsgs(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
+                                                 iteration, dist_thres=opt.dist_thres, prune_from_iter=opt.prune_from_iter,
+                                                 proximity_until_iter=opt.proximity_until_iter, generator=gen,
+                                                 on_device=bool(opt.densify_on_device))
+        m.update_learning_rate(iteration, opt.position_lr_final, opt.position_lr_delay_mult, opt.position_lr_max_steps)
+        reset = (iteration - opt.start_sample_pseudo - 1) % opt.opacity_reset_interval == 0 and iteration > opt.start_sample_pseudo
+        if reset:
+            m.reset_opacity(opt.opacity_reset_value)
+        return dict(loss=loss, camera=ci, sh_degree=m.active_sh_degree, xyz_lr=lr_used, depth_weight=weight_used,
+                    stepped=do_step, densified=densified, reset=reset, pseudo=entered, path=self.last["path"], P=m.P)
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # hipGraph replay of the steady-state single-GPU step
 # ----------------------------------------------------------------------------------------------------------------
 def _status_check(tag, num_rendered, overflow, trunc_failed):
@@ -2471,6 +2722,8 @@ class GraphedStep:
         """capacity: binning capacity (instances) to capture with; default = capacity_margin x the largest view the
         backend has seen recently.  warmup: un-captured steps before the FIRST capture (allocator and library state
         settle); every later camera takes one."""
+        if isinstance(trainer, TrainerFSGS):
+            raise RuntimeError("GraphedStep (hipGraph replay) is closed to the FSGS rasterizer generation's trainer")
         self.tr = trainer
         trainer._graphed = self   # Trainer.sync() settles the last replay too
         self.fixed_capacity = capacity
