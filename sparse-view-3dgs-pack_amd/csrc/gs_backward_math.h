@@ -273,7 +273,9 @@ GS_DEV Cov2DBack cov2d_backward(V3 mean, const SymD& Sg, const float* vm, float 
 // With r_j the j-th column of R:  Sigma = sum_j s_j^2 r_j r_j^T  =>  dL/ds_j = 2 s_j r_j^T G r_j  and
 // D = dL/dR = 2 G R diag(s)^2; the quaternion gradient contracts D with dR/dq.
 // quirk: dL/ds is returned w.r.t. s itself, without the factor scale_modifier (backward.cu:372-375) - the same thing on
-// the training path (scale_modifier = 1); tests/test_oracle_golden.py pins it against the reference's python autograd.
+// the training path (scale_modifier = 1); tests/test_oracle_golden.py pins it against the reference's python autograd, and
+// tests/test_gpu_input_forms.py pins the kernels on it (modifiers 0.6 and 1.8 against the CPU checker, which
+// tests/test_form_cases_cpu.py holds to float64 x 1 / modifier; host run: tests/test_backward_math_host.py).
 GS_DEV void cov3d_backward(const SymD& G, D3 s, const RotD& R, V4 quat, V3& dscale, float dq[4]) {
 #pragma clang fp contract(fast)
   const double r = quat.x, x = quat.y, y = quat.z, z = quat.w;

@@ -106,15 +106,18 @@ def exact_T(oracle):
 _ORACLE = {}
 
 
-def oracle_case(oracle, name, which="scene_sr"):
+def oracle_case(oracle, name, which="scene_sr", modifier=None):
     """One constructed scene (tests/blend_cases.py; its scales + rotations form, or `scene`: its covariances; its own opacities) through the checker's
     FSGS generation in the exact-transmittance form and through the float64 model, both gradient families at once.
+    modifier: the scene under that scale modifier (None: as built).
     -> dict(dense outputs, dense grads, oracle result, d_ref{tensor: the checker's distance to float64}); cached."""
-    key = (name, which)
+    key = (name, which) if modifier is None else (name, which, float(modifier))
     if key not in _ORACLE:
         import blend_cases
         case = blend_cases.build(name)
         sc = getattr(case, which)
+        if modifier is not None:
+            sc = dict(sc, scale_modifier=float(modifier))
         dd, da = cotangents(case.H, case.W, 4000 + blend_cases.NAMES.index(name))
         dn, dg = dense_pass(sc, case.cam, case.bg, dd, da)
         with exact_T(oracle):

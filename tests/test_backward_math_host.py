@@ -38,6 +38,13 @@ CASES = [
     dict(P=200, seed=13, W=64, H=64, aa=True, depth_mode=0, deg=1),
     dict(P=200, seed=14, W=64, H=48, aa=False, depth_mode=2, deg=2),
     dict(P=150, seed=15, W=64, H=48, aa=True, depth_mode=1, deg=0, precomp=True, mod=0.8),
+    # a scale modifier on own scales and rotations (chain_from_row: s = modifier x scale; dL_dscales without the factor)
+    dict(P=300, seed=16, W=96, H=64, aa=False, depth_mode=1, deg=3, mod=1.8),
+    dict(P=300, seed=17, W=80, H=72, aa=True, depth_mode=2, deg=2, mod=0.6),
+    # SH rows of 1, 4 and 9 coefficients (sh_backward_row's generic-M reader), cut after trained_like
+    dict(P=200, seed=18, W=64, H=48, aa=False, depth_mode=0, deg=0, rows=1),
+    dict(P=200, seed=19, W=64, H=64, aa=True, depth_mode=1, deg=1, rows=4),
+    dict(P=200, seed=20, W=64, H=48, aa=False, depth_mode=2, deg=2, rows=9),
 ]
 
 
@@ -45,9 +52,11 @@ CASES = [
 def test_host_run_of_the_kernel_math_matches_the_oracle_stage_two(oracle, host_math, case):
     P, W, H = case["P"], case["W"], case["H"]
     sc = synthetic.trained_like(P, seed=case["seed"], sh_degree=case["deg"], scale_mult=1.5)
-    sc["scale_modifier"] = case.get("mod", 1.0)
+    if case.get("rows"):
+        sc["shs"] = sc["shs"][:, :case["rows"], :].contiguous()
     if case.get("precomp"):
         sc = small_scene(P, case["seed"], precomp_color=True, precomp_cov=True)
+    sc["scale_modifier"] = case.get("mod", 1.0)   # (after the scene is final: the modifier reaches every call below)
     cam = synthetic.look_at_camera((2.6, 1.1, 0.9), W, H)
     be = oracle.backend
     cpu = torch.device("cpu")
