@@ -92,11 +92,13 @@ __device__ inline uint32_t grid_index(int D, uint32_t gridtype, bool align_corne
   return index % hashmap_size;
 }
 
-// Position of point x at one level: integer cell, (smoothstep'd) fraction and its derivative factor.
+// Position of point x at one level: integer cell, (smoothstep'd) fraction, its complement and its derivative factor.
+// The complement under smoothstep is s(1 - p) = 1 - s(p): next to a cell face 1 - s(p) cancels and the left corner's
+// weight (and with it a slot's whole gradient, when that corner is its only entry) would lose its relative accuracy.
 // Returns false when a coordinate lies outside [0, 1].
 template <int D>
 __device__ inline bool grid_locate(const float* x, float scale, bool align_corners, uint32_t interp, uint32_t* cell,
-                                   float* frac, float* dfrac) {
+                                   float* frac, float* cfrac, float* dfrac) {
   bool in = true;
 #pragma unroll
   for (int d = 0; d < D; d++) in = in && !(x[d] < 0.0f || x[d] > 1.0f);
@@ -107,22 +109,25 @@ __device__ inline bool grid_locate(const float* x, float scale, bool align_corne
     const float fl = floorf(p);
     cell[d] = (uint32_t)fl;
     p -= fl;
+    const float q = 1.0f - p;
     if (interp == 1) {
-      dfrac[d] = 6.0f * p * (1.0f - p);
+      dfrac[d] = 6.0f * p * q;
       frac[d] = p * p * (3.0f - 2.0f * p);
+      cfrac[d] = q * q * (3.0f - 2.0f * q);
     } else {
       dfrac[d] = 1.0f;
       frac[d] = p;
+      cfrac[d] = q;
     }
   }
   return true;
 }
 
 template <int D>
-__device__ inline float corner_weight(const float* frac, uint32_t corner) {
+__device__ inline float corner_weight(const float* frac, const float* cfrac, uint32_t corner) {
   float w = 1.0f;
 #pragma unroll
-  for (int d = 0; d < D; d++) w *= (corner >> d) & 1u ? frac[d] : 1.0f - frac[d];
+  for (int d = 0; d < D; d++) w *= (corner >> d) & 1u ? frac[d] : cfrac[d];
   return w;
 }
 
@@ -141,10 +146,10 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_fwd_kernel(const float* __restr
 #pragma unroll
   for (int d = 0; d < D; d++) x[d] = inputs[b * D + d];
   uint32_t cell[D];
-  float frac[D], dfrac[D];
+  float frac[D], cfrac[D], dfrac[D];
   float* o = out + t * C;
   float* g = dy_dx ? dy_dx + t * (D * C) : nullptr;
-  if (!grid_locate<D>(x, lv.scale[l], align_corners, interp, cell, frac, dfrac)) {
+  if (!grid_locate<D>(x, lv.scale[l], align_corners, interp, cell, frac, cfrac, dfrac)) {
 #pragma unroll
     for (int c = 0; c < C; c++) o[c] = 0.0f;
     if (g)
@@ -165,7 +170,7 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_fwd_kernel(const float* __restr
 #pragma unroll
     for (int d = 0; d < D; d++) cc[d] = cell[d] + ((k >> d) & 1u);
     const size_t row = base + grid_index(D, gridtype, align_corners, hsize, res, cc);
-    const float w = corner_weight<D>(frac, k);
+    const float w = corner_weight<D>(frac, cfrac, k);
 #pragma unroll
     for (int c = 0; c < C; c++) {
       val[k][c] = emb[row * C + c];
@@ -187,7 +192,7 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_fwd_kernel(const float* __restr
       float w = scale;
 #pragma unroll
       for (int d = 0; d < D; d++)
-        if (d != gd) w *= (k >> d) & 1u ? frac[d] : 1.0f - frac[d];
+        if (d != gd) w *= (k >> d) & 1u ? frac[d] : cfrac[d];
 #pragma unroll
       for (int c = 0; c < C; c++) r[c] += w * (val[k | (1u << gd)][c] - val[k][c]) * dfrac[gd];
     }
@@ -211,8 +216,8 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_emit_kernel(const float* __rest
 #pragma unroll
   for (int d = 0; d < D; d++) x[d] = inputs[b * D + d];
   uint32_t cell[D];
-  float frac[D], dfrac[D];
-  const bool in = grid_locate<D>(x, lv.scale[l], align_corners, 0, cell, frac, dfrac);
+  float frac[D], cfrac[D], dfrac[D];
+  const bool in = grid_locate<D>(x, lv.scale[l], align_corners, 0, cell, frac, cfrac, dfrac);
   const uint32_t base = (uint32_t)offsets[l];
   const uint32_t hsize = (uint32_t)offsets[l + 1] - base;
 #pragma unroll
@@ -251,9 +256,9 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_gather_kernel(const float* __re
 #pragma unroll
     for (int d = 0; d < D; d++) x[d] = inputs[(size_t)b * D + d];
     uint32_t cell[D];
-    float frac[D], dfrac[D];
-    grid_locate<D>(x, lv.scale[l], align_corners, interp, cell, frac, dfrac);
-    const float w = corner_weight<D>(frac, k);
+    float frac[D], cfrac[D], dfrac[D];
+    grid_locate<D>(x, lv.scale[l], align_corners, interp, cell, frac, cfrac, dfrac);
+    const float w = corner_weight<D>(frac, cfrac, k);
 #pragma unroll
     for (int c = 0; c < C; c++) v[c] = w * grad[(size_t)t * C + c];
   }
@@ -336,9 +341,11 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_input_bwd_kernel(const float* _
 }
 
 // ---- spherical harmonics: Y_l^m = (-1)^m K_lm Pbar_l^|m|(z) * {Re, Im}((x + i y)^|m|), the r^2 -> 1 polynomial forms ----
+// Evaluated in double and rounded once: the recurrences below are three fp32 ulps off a band-7 value otherwise, and the
+// kernels are bound by their 4 * deg^2 bytes per point either way.
 #define SH_MAX_DEG 8
 struct ShNorm {
-  float k[SH_MAX_DEG * (SH_MAX_DEG + 1) / 2];  // [l (l + 1) / 2 + m]: sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!), x sqrt(2) for m > 0
+  double k[SH_MAX_DEG * (SH_MAX_DEG + 1) / 2];  // [l (l + 1) / 2 + m]: sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!), x sqrt(2) for m > 0
 };
 
 static ShNorm sh_norm() {
@@ -349,7 +356,7 @@ static ShNorm sh_norm() {
       for (int i = l - m + 1; i <= l + m; i++) r /= (double)i;
       double k = std::sqrt((2.0 * l + 1.0) / (4.0 * M_PI) * r);
       if (m > 0) k *= std::sqrt(2.0);
-      n.k[l * (l + 1) / 2 + m] = (float)k;
+      n.k[l * (l + 1) / 2 + m] = k;
     }
   return n;
 }
@@ -357,56 +364,58 @@ static ShNorm sh_norm() {
 // Pbar_l^m(z) for l < deg, and its z-derivative: Pbar_m^m = (-1)^m (2m-1)!!, Pbar_{m+1}^m = (2m+1) z Pbar_m^m,
 // (l - m) Pbar_l^m = (2l - 1) z Pbar_{l-1}^m - (l + m - 1) Pbar_{l-2}^m.  A_m + i B_m = (x + i y)^m.
 template <bool GRAD>
-__device__ inline void sh_eval(float x, float y, float z, int deg, const ShNorm& nm, const float* gout, float* out,
+__device__ inline void sh_eval(double x, double y, double z, int deg, const ShNorm& nm, const float* gout, float* out,
                                float* gx, float* gy, float* gz) {
-  float A[SH_MAX_DEG], Bm[SH_MAX_DEG];
-  A[0] = 1.0f;
-  Bm[0] = 0.0f;
+  double A[SH_MAX_DEG], Bm[SH_MAX_DEG];
+  A[0] = 1.0;
+  Bm[0] = 0.0;
   for (int m = 1; m < deg; m++) {
     A[m] = x * A[m - 1] - y * Bm[m - 1];
     Bm[m] = x * Bm[m - 1] + y * A[m - 1];
   }
-  float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-  float pmm = 1.0f;  // Pbar_m^m
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  double pmm = 1.0;  // Pbar_m^m
   for (int m = 0; m < deg; m++) {
-    if (m > 0) pmm *= -(float)(2 * m - 1);
-    float p2 = 0.0f, d2 = 0.0f, p1 = pmm, d1 = 0.0f;  // Pbar_{l-2}, Pbar_{l-1} and their derivatives
+    if (m > 0) pmm *= -(double)(2 * m - 1);
+    double p2 = 0.0, d2 = 0.0, p1 = pmm, d1 = 0.0;  // Pbar_{l-2}, Pbar_{l-1} and their derivatives
     for (int l = m; l < deg; l++) {
-      float p, dp;
+      double p, dp;
       if (l == m) {
         p = pmm;
-        dp = 0.0f;
+        dp = 0.0;
       } else {
-        p = ((float)(2 * l - 1) * z * p1 - (float)(l + m - 1) * p2) / (float)(l - m);
-        dp = ((float)(2 * l - 1) * (p1 + z * d1) - (float)(l + m - 1) * d2) / (float)(l - m);
+        p = ((double)(2 * l - 1) * z * p1 - (double)(l + m - 1) * p2) / (double)(l - m);
+        dp = ((double)(2 * l - 1) * (p1 + z * d1) - (double)(l + m - 1) * d2) / (double)(l - m);
         p2 = p1;
         d2 = d1;
       }
       p1 = p;
       d1 = dp;
-      const float k = nm.k[l * (l + 1) / 2 + m];
+      const double k = nm.k[l * (l + 1) / 2 + m];
       const int jp = l * l + l + m, jn = l * l + l - m;
       if (!GRAD) {
-        out[jp] = k * p * A[m];
-        if (m > 0) out[jn] = k * p * Bm[m];
+        out[jp] = (float)(k * p * A[m]);
+        if (m > 0) out[jn] = (float)(k * p * Bm[m]);
       } else {
-        const float dA_dx = m > 0 ? (float)m * A[m - 1] : 0.0f, dA_dy = m > 0 ? -(float)m * Bm[m - 1] : 0.0f;
-        sx += gout[jp] * k * p * dA_dx;
-        sy += gout[jp] * k * p * dA_dy;
-        sz += gout[jp] * k * dp * A[m];
+        const double dA_dx = m > 0 ? (double)m * A[m - 1] : 0.0, dA_dy = m > 0 ? -(double)m * Bm[m - 1] : 0.0;
+        const double gp = (double)gout[jp];
+        sx += gp * k * p * dA_dx;
+        sy += gp * k * p * dA_dy;
+        sz += gp * k * dp * A[m];
         if (m > 0) {
-          const float dB_dx = (float)m * Bm[m - 1], dB_dy = (float)m * A[m - 1];
-          sx += gout[jn] * k * p * dB_dx;
-          sy += gout[jn] * k * p * dB_dy;
-          sz += gout[jn] * k * dp * Bm[m];
+          const double dB_dx = (double)m * Bm[m - 1], dB_dy = (double)m * A[m - 1];
+          const double gn = (double)gout[jn];
+          sx += gn * k * p * dB_dx;
+          sy += gn * k * p * dB_dy;
+          sz += gn * k * dp * Bm[m];
         }
       }
     }
   }
   if (GRAD) {
-    *gx = sx;
-    *gy = sy;
-    *gz = sz;
+    *gx = (float)sx;
+    *gy = (float)sy;
+    *gz = (float)sz;
   }
 }
 

@@ -6,6 +6,8 @@ exp2(l * S) * H - 1 from the fp32 product l * S, pos = x * scale + 0.5 / 0, its 
 hashing); interpolation and every sum run in float64 with torch autograd, which also gives the embedding and input
 gradients.  The input gradient flows through the fraction with d(frac)/dx = scale (smoothstep: its derivative too):
 frac = fp32 fraction + (x - fp32(x)) * scale, which is the fp32 fraction itself for fp32 inputs.
+The left corner's factor under smoothstep is s(1 - p), which is 1 - s(p) exactly (s(p) = p^2 (3 - 2 p)) and keeps its
+relative accuracy next to a cell face, where 1 - s(p) cancels: float64's 1 - s(p) is itself 1e-5 off such a factor.
 
 SH: the general Cartesian real-SH formula with the r^2 -> 1 substitution and the reference's sign (band 1 is
 (-C1 y, C1 z, -C1 x), the Condon-Shortley phase (-1)^m), evaluated as written for non-unit inputs too:
@@ -70,13 +72,15 @@ def _slot(cell, D, gridtype, align_corners, hsize, res):
 
 
 def grid_encode_ref(inputs, embeddings, offsets, per_level_scale, H, gridtype=0, align_corners=False, interpolation=0,
-                    fp32_cells=True):
+                    fp32_cells=True, dtype=torch.float64):
     """inputs [B,D] in [0,1] (fp32 or fp64, may require grad), embeddings [n_slots,C] (any float, may require grad)
     -> float64 [B, L*C].  fp32_cells=False places the points in float64 throughout (for gradcheck, whose float64
-    perturbations are below the fp32 rounding of the position)."""
+    perturbations are below the fp32 rounding of the position).  dtype=torch.float32 forms every product and sum
+    (smoothstep, corner weights, the interpolation and, through autograd, both gradients) in fp32 instead: one fp32
+    order among many, the yardstick of tests/encoding_cases.py's measured bars; the result is then fp32."""
     x32 = inputs.detach().float()
-    xg = inputs.double()
-    emb = embeddings.double()
+    xg = inputs.to(dtype)
+    emb = embeddings.to(dtype)
     B, D = x32.shape
     L = len(offsets) - 1
     oob = ((x32 < 0) | (x32 > 1)).any(dim=1)
@@ -89,18 +93,19 @@ def grid_encode_ref(inputs, embeddings, offsets, per_level_scale, H, gridtype=0,
         fl = torch.floor(pos.detach())
         cell = fl.long()
         if fp32_cells:
-            frac = (pos - fl).double() + (xg - xs.double()) * float(sc)  # (zero for fp32 inputs; carries d/dx = scale)
+            frac = (pos - fl).to(dtype) + (xg - xs.to(dtype)) * float(sc)  # (zero for fp32 inputs; carries d/dx = scale)
         else:
             frac = pos - fl
+        cfrac = 1.0 - frac
         if interpolation == 1:
-            frac = frac * frac * (3.0 - 2.0 * frac)
+            frac, cfrac = frac * frac * (3.0 - 2.0 * frac), cfrac * cfrac * (3.0 - 2.0 * cfrac)
         base, hsize = offsets[l], offsets[l + 1] - offsets[l]
         acc = 0.0
         for k in range(1 << D):
             bits = torch.tensor([(k >> d) & 1 for d in range(D)], dtype=torch.int64, device=cell.device)
-            w = torch.ones((B,), dtype=torch.float64, device=cell.device)
+            w = torch.ones((B,), dtype=dtype, device=cell.device)
             for d in range(D):
-                w = w * (frac[:, d] if (k >> d) & 1 else 1.0 - frac[:, d])
+                w = w * (frac[:, d] if (k >> d) & 1 else cfrac[:, d])
             rows = base + _slot(cell + bits, D, gridtype, align_corners, hsize, res)
             acc = acc + w[:, None] * emb[rows]
         outs.append(torch.where(oob[:, None], torch.zeros_like(acc), acc))
@@ -118,9 +123,10 @@ def _pi_coeffs(l, m):
     return out
 
 
-def sh_encode_ref(inputs, degree):
-    """inputs [B,3] (any float, may require grad) -> float64 [B, degree^2]."""
-    v = inputs.double()
+def sh_encode_ref(inputs, degree, dtype=torch.float64):
+    """inputs [B,3] (any float, may require grad) -> float64 [B, degree^2]; dtype=torch.float32: the same statements with
+    every product and sum in fp32 (the yardstick of the per-column bars of tests/encoding_cases.py)."""
+    v = inputs.to(dtype)
     x, y, z = v[:, 0], v[:, 1], v[:, 2]
     out = [None] * (degree * degree)
     for l in range(degree):
