@@ -299,6 +299,27 @@ int gs_depth_backward(const GsView* view, const GsGaussians* g, const int32_t* r
                       const float* dL_dalpha, int grad_flags, float* dL_dmeans3D, float* dL_dmeans2D,
                       float* dL_dopacity, void* workspace, size_t workspace_bytes, void* stream);
 
+/* gs_depth_backward with the optimizer step of a DNGaussian depth leg in its tail (train_llff.py:104-135: each leg's backward is
+ * followed by an Adam step of ONE tensor).  Row zeroing and blend backward are gs_depth_backward's; the per-Gaussian launch then
+ * steps the row it has just differentiated.  Additive; device library only.
+ *   which 1: gradient to the means; param / exp_avg / exp_avg_sq [P,3] (param may be g->means3D itself).
+ *   which 2: gradient to the opacities; param / moments [P] are the RAW opacity row, g->opacities its sigmoid: the gradient of
+ *            the raw row is dL_dopacity * (1 - s) * s, gs_activations_bwd's expression.
+ * The row's gradient has the bits gs_depth_backward writes (zero for culled rows and rows without instances); the update is
+ * the rule at gs_adam_step_tensors with flags == 0, coefficients formed from (lr, step) as gs_adam_step forms them, so
+ * parameters and moments equal gs_depth_backward [+ the sigmoid line] + gs_adam_step bit for bit.  EVERY row is stepped: a zero
+ * gradient still decays the moments and moves the parameter.  No gradient array and no dL_dmeans2D is written.
+ * flags: GS_DEPTH_STEP_ROWS_GIVEN - the float64 rows in `workspace` are taken as they are (as a gs_depth_backward of the same
+ * scratch and cotangents left them): no zeroing, no blend; dL_ddepth / dL_dalpha may then be NULL.
+ * workspace as gs_depth_backward.  Status codes, no launch: gs_depth_backward's, and NULL param / moments -> GS_E_NULL; which
+ * outside 1..2 or step < 1 -> GS_E_SHAPE; an unknown flag bit -> GS_E_UNSUPPORTED.  P == 0: GS_OK, nothing launched. */
+#define GS_DEPTH_STEP_ROWS_GIVEN 1
+int gs_depth_backward_step(const GsView* view, const GsGaussians* g, const int32_t* radii,
+                           const GsScratch* scratch, int64_t num_rendered, const float* dL_ddepth,
+                           const float* dL_dalpha, int which, float* param, float* exp_avg, float* exp_avg_sq,
+                           float lr, int32_t step, float beta1, float beta2, float eps, int32_t flags,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* present[i] = (view-space z of means3D[i]) > 0.2   (rasterizer_impl.cu:54-66) */
 int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix,
                     const float* projmatrix, uint8_t* present, void* stream);

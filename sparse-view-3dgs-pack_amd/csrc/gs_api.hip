@@ -738,6 +738,85 @@ int gs_depth_backward(const GsView* v, const GsGaussians* g, const int32_t* radi
   return GS_OK;
 }
 
+// gs_depth_backward with Adam on the leg's one tensor in the tail: row zeroing and blend as above, then ONE per-Gaussian launch
+// that steps the row it has just differentiated; no gradient array exists.
+int gs_depth_backward_step(const GsView* v, const GsGaussians* g, const int32_t* radii, const GsScratch* sc, int64_t num_rendered,
+                           const float* dL_ddepth, const float* dL_dalpha, int which, float* param, float* exp_avg,
+                           float* exp_avg_sq, float lr, int32_t step, float beta1, float beta2, float eps, int32_t flags,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+  if (v && v->antialiasing) return GS_E_UNSUPPORTED;
+  if (which < 1 || which > 2 || step < 1) return GS_E_SHAPE;
+  if (flags & ~GS_DEPTH_STEP_ROWS_GIVEN) return GS_E_UNSUPPORTED;
+  if (!param || !exp_avg || !exp_avg_sq) return GS_E_NULL;
+  int rc = depth_pass_args(v, g);
+  if (rc) return rc;
+  if (!sc) return GS_E_NULL;
+  const int P = g->P, W = v->image_width, H = v->image_height;
+  if (P == 0) return GS_OK;
+  if (!radii || !sc->geom || !sc->img || !workspace) return GS_E_NULL;
+  if (workspace_bytes < gs_align((size_t)P * GR_ROW_BYTES)) return GS_E_SCRATCH;
+  if (num_rendered < 0 || num_rendered > sc->binning_capacity) return GS_E_SHAPE;
+  if (num_rendered > 0 && !sc->binning) return GS_E_NULL;
+  hipStream_t s = (hipStream_t)stream;
+  int gx, gy;
+  tile_grid(v, gx, gy);
+  const size_t T = (size_t)gx * gy, N = (size_t)W * H;
+  if (sc->geom_bytes < geom_bytes((size_t)P) || sc->img_bytes < img_bytes(N, T)) return GS_E_SCRATCH;
+  GeomView gv = geom_view(sc->geom, (size_t)P);
+  ImgView iv = img_view(sc->img, N, T);
+  SortBufs bv = sort_view(sc->binning, (size_t)sc->binning_capacity);
+  gs_row_t* rows = (gs_row_t*)workspace;
+  if (!(flags & GS_DEPTH_STEP_ROWS_GIVEN)) {
+    {
+      GS_PROF(ST_BWD_MEMSET, s);
+      launch_zero_rows(rows, (size_t)P, v->tile_cull ? gv.tiles_touched : nullptr, s);
+    }
+    if (num_rendered > 0) {
+      GS_PROF(ST_RENDER_BWD, s);
+      launch_depth_bwd(iv.ranges, bv.vals[0], W, H, gx, gy, gv.splat, iv.final_T, iv.n_contrib, iv.tile_work, iv.tile_order,
+                       dL_ddepth, dL_dalpha, rows, which, s);
+    }
+    GS_LAUNCH_CHECK(s, v->debug);
+  }
+  DepthPointArgs a;
+  a.P = P;
+  a.means3D = g->means3D;
+  a.radii = radii;
+  a.scales = g->scales;
+  a.rotations = g->rotations;
+  a.scale_modifier = v->scale_modifier;
+  a.cov3D = g->cov3D_precomp;
+  a.viewmatrix = v->viewmatrix;
+  a.projmatrix = v->projmatrix;
+  a.focal_y = v->image_height / (2.0f * v->tanfovy);
+  a.focal_x = v->image_width / (2.0f * v->tanfovx);
+  a.tan_fovx = v->tanfovx;
+  a.tan_fovy = v->tanfovy;
+  a.skip_uninstanced = v->tile_cull ? 1 : 0;
+  a.tiles_touched = gv.tiles_touched;
+  a.grad_rows = rows;
+  a.dL_dmeans3D = a.dL_dmeans2D = a.dL_dopacity = nullptr;
+  DepthStepArgs st;
+  st.param = param;
+  st.exp_avg = exp_avg;
+  st.exp_avg_sq = exp_avg_sq;
+  st.activated = g->opacities;
+  {  // (as gs_adam_step forms them: double, rounded once; the product with lr in float)
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    st.lr_bc1 = lr * (float)(1.0 / bc1);
+    st.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  }
+  st.b1 = beta1;
+  st.b2 = beta2;
+  st.eps = eps;
+  {
+    GS_PROF(ST_PREPROCESS_BWD, s);
+    launch_depth_point_step(a, st, which, s);
+  }
+  GS_LAUNCH_CHECK(s, v->debug);
+  return GS_OK;
+}
+
 int gs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* /*projmatrix*/,
                     uint8_t* present, void* stream) {
   if (P < 0) return GS_E_SHAPE;

@@ -367,6 +367,15 @@ struct DepthPointArgs {
   float* dL_dopacity;      // [P]    (grad_flags & 2)
 };
 int launch_depth_point_bwd(const DepthPointArgs& a, int grad_flags, hipStream_t s);
+// gs_depth_backward_step: the one tensor the tail steps, Adam's coefficients as gs_adam_step forms them
+struct DepthStepArgs {
+  float* param;            // which 1: [P,3] means, 2: [P] raw opacities
+  float* exp_avg;
+  float* exp_avg_sq;
+  const float* activated;  // which 2: the activated opacities [P]
+  float lr_bc1, inv_sqrt_bc2, b1, b2, eps;
+};
+int launch_depth_point_step(const DepthPointArgs& a, const DepthStepArgs& st, int which, hipStream_t s);
 
 int launch_blend_stats(const uint2* ranges, const uint32_t* point_list, int W, int H, int grid_x, int grid_y, const Splat* splat,
                        const uint32_t* n_contrib, const uint32_t* tile_work, unsigned long long* out, hipStream_t s);

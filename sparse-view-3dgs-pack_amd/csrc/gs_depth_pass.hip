@@ -14,6 +14,9 @@
 //                             sums, no background term; six sums per (tile, Gaussian) for the means, one for the opacities.
 //   depth_point_bwd_kernel  = the per-Gaussian tail, one thread per Gaussian: cov2D backward (float64, mean part only),
 //                             projection backward, the depth term; no cov3D backward, no SH, no colour.
+//   depth_point_step_kernel = that tail with Adam on the ONE tensor a DNGaussian depth leg steps (the means, or the raw
+//                             opacities through the sigmoid's backward) in place of the gradient stores
+//                             (gs_depth_backward_step).
 // Same tile mapping, lists, splat records, alpha rules and float64 gradient rows as the general path (gs_render_fwd_wave.hip,
 // gs_render_bwd_wave.hip, gs_backward_math.h).
 //
@@ -387,13 +390,14 @@ int launch_depth_bwd(const uint2* ranges, const uint32_t* point_list, int W, int
 // ------------------------------------------------------------------------------------------------------------------
 // per-Gaussian tail: one thread per Gaussian, every output row written (zeros for culled rows and rows without instances)
 // ------------------------------------------------------------------------------------------------------------------
+// The row's gradient from its float64 sums: dL/dmean (GRAD_MEANS; mx, my = dL/dmean2D) and dL/d(activated opacity)
+// (GRAD_OPACITY).  One copy of the expressions for the kernel that writes the gradients and the one that steps with them: the
+// file is built without contraction, so both round alike.
 template <bool GRAD_MEANS, bool GRAD_OPACITY>
-__global__ void __launch_bounds__(GS_BLOCK) depth_point_bwd_kernel(DepthPointArgs a) {
-  const int idx = blockIdx.x * GS_BLOCK + threadIdx.x;
-  if (idx >= a.P) return;
+__device__ __forceinline__ void depth_point_grad(const DepthPointArgs& a, int idx, V3& dmean, float& mx, float& my, float& dop) {
   const bool active = a.radii[idx] > 0 && !(a.skip_uninstanced && a.tiles_touched[idx] == 0);
-  V3 dmean = {0.f, 0.f, 0.f};
-  float mx = 0.f, my = 0.f, dop = 0.f;
+  dmean = {0.f, 0.f, 0.f};
+  mx = my = dop = 0.f;
   if (active) {
     const double2* gr = reinterpret_cast<const double2*>(a.grad_rows + (size_t)idx * GR_STRIDE);
     if (GRAD_OPACITY) dop = (float)gr[2].y;  // [cyy op]
@@ -429,6 +433,15 @@ __global__ void __launch_bounds__(GS_BLOCK) depth_point_bwd_kernel(DepthPointArg
       dmean = dmean + projection_backward(mean, a.projmatrix, mx, my);
     }
   }
+}
+
+template <bool GRAD_MEANS, bool GRAD_OPACITY>
+__global__ void __launch_bounds__(GS_BLOCK) depth_point_bwd_kernel(DepthPointArgs a) {
+  const int idx = blockIdx.x * GS_BLOCK + threadIdx.x;
+  if (idx >= a.P) return;
+  V3 dmean;
+  float mx, my, dop;
+  depth_point_grad<GRAD_MEANS, GRAD_OPACITY>(a, idx, dmean, mx, my, dop);
   if (GRAD_MEANS) {
     a.dL_dmeans3D[3 * idx] = dmean.x;
     a.dL_dmeans3D[3 * idx + 1] = dmean.y;
@@ -445,5 +458,63 @@ int launch_depth_point_bwd(const DepthPointArgs& a, int grad_flags, hipStream_t 
   if (grad_flags == 3) hipLaunchKernelGGL((depth_point_bwd_kernel<true, true>), grid, dim3(GS_BLOCK), 0, s, a);
   else if (grad_flags == 1) hipLaunchKernelGGL((depth_point_bwd_kernel<true, false>), grid, dim3(GS_BLOCK), 0, s, a);
   else hipLaunchKernelGGL((depth_point_bwd_kernel<false, true>), grid, dim3(GS_BLOCK), 0, s, a);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// gs_depth_backward_step's tail: depth_point_bwd_kernel with Adam on the ONE tensor the depth leg steps in place of the gradient
+// stores.  WHICH 1: param = the means [P,3]; 2: param = the raw opacities [P], the activated ones (g->opacities) give the
+// sigmoid's backward in gs_activations_bwd's expression.  Every row is stepped (a zero gradient decays the moments).
+// A workgroup owns GS_BLOCK consecutive Gaussians, so GS_BLOCK * 3 (or GS_BLOCK) floats of param / exp_avg / exp_avg_sq in one piece: each
+// thread leaves its row's gradient in LDS and the workgroup then walks the piece one dword per lane, consecutive lanes on
+// consecutive addresses - the [P,3] rows are 12 bytes apart and start on no vector boundary, so a per-thread row access would
+// be three strided dword instructions per array.  Arithmetic: gs_adam.hip's adam_element, this file too is built without
+// contraction.
+// ------------------------------------------------------------------------------------------------------------------
+template <int WHICH>
+__global__ void __launch_bounds__(GS_BLOCK) depth_point_step_kernel(DepthPointArgs a, DepthStepArgs st) {
+  constexpr int N = WHICH == 1 ? 3 : 1;
+  __shared__ float s_g[GS_BLOCK * N];
+  const int first = blockIdx.x * GS_BLOCK;
+  const int idx = first + threadIdx.x;
+  if (idx < a.P) {
+    V3 dmean;
+    float mx, my, dop;
+    depth_point_grad<WHICH == 1, WHICH == 2>(a, idx, dmean, mx, my, dop);
+    if (WHICH == 1) {
+      s_g[3 * threadIdx.x] = dmean.x;
+      s_g[3 * threadIdx.x + 1] = dmean.y;
+      s_g[3 * threadIdx.x + 2] = dmean.z;
+    } else {
+      const float s = st.activated[idx];  // sigmoid backward: grad * (1 - s) * s
+      s_g[threadIdx.x] = dop * (1.0f - s) * s;
+    }
+  }
+  __syncthreads();  // (WHICH 1: every read of the means above precedes the stores below - param may BE a.means3D)
+  const int cnt = min(GS_BLOCK, a.P - first) * N;
+  float* __restrict__ p = st.param + (size_t)first * N;
+  float* __restrict__ m = st.exp_avg + (size_t)first * N;
+  float* __restrict__ v = st.exp_avg_sq + (size_t)first * N;
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const int j = k * GS_BLOCK + threadIdx.x;
+    if (j < cnt) {
+      float pe = p[j], me = m[j], ve = v[j];
+      const float g = s_g[j];
+      me = st.b1 * me + (1.f - st.b1) * g;
+      ve = st.b2 * ve + (1.f - st.b2) * g * g;
+      const float denom = sqrtf(ve) * st.inv_sqrt_bc2 + st.eps;
+      pe = pe - st.lr_bc1 * (me / denom);
+      p[j] = pe;
+      m[j] = me;
+      v[j] = ve;
+    }
+  }
+}
+
+int launch_depth_point_step(const DepthPointArgs& a, const DepthStepArgs& st, int which, hipStream_t s) {
+  const dim3 grid((a.P + GS_BLOCK - 1) / GS_BLOCK);
+  if (which == 1) hipLaunchKernelGGL((depth_point_step_kernel<1>), grid, dim3(GS_BLOCK), 0, s, a, st);
+  else hipLaunchKernelGGL((depth_point_step_kernel<2>), grid, dim3(GS_BLOCK), 0, s, a, st);
   return 0;
 }

@@ -101,6 +101,7 @@ class GsAdamTensor(C.Structure):
 
 
 ADAM_NO_BIAS_CORRECTION = 1   # GS_ADAM_NO_BIAS_CORRECTION
+DEPTH_STEP_ROWS_GIVEN = 1     # GS_DEPTH_STEP_ROWS_GIVEN
 ADAM_MAX_TENSORS = 8          # tensors per gs_adam_step_tensors call
 
 
@@ -149,6 +150,8 @@ PROTOTYPES = {
     "depth_forward": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P, _P]),
     "depth_backward": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, C.c_int,
                                  _P, _P, _P, _P, _SZ, _P]),
+    "depth_backward_step": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, C.c_int,
+                                      _P, _P, _P, _F, _I32, _F, _F, _F, _I32, _P, _SZ, _P]),
     "step_uninstanced": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch),
                                    C.POINTER(GsStepState), _P]),
     "backward_step": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P,
@@ -313,6 +316,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",
+               # a depth leg's backward with its one-tensor Adam step in the tail: compared on the GPU against gs_depth_backward +
+               # gs_adam_step, bit for bit (tests/test_gpu_dng_step.py)
+               "depth_backward_step",
                # the reference-API optimizer's one-launch step (restated in numpy: tests/sparse_adam_reference.py) and the backward
                # for the model's split SH rows - a memory layout of the product, compared against gs_backward's slices on the GPU
                "adam_step_tensors", "backward_split",

@@ -7,6 +7,9 @@ the opacities): constant colour 1, colour image never used, scales and rotations
 them too, through the general kernels; this module is the opt-in, leaner form.  `dgr_dng.render_for_depth` /
 `dgr_dng.render_for_opa` wrap it under the reference's names.
 
+`depth_leg_step` is a whole depth leg of DNGaussian's loop - forward, loss, backward and the Adam step of the leg's one tensor
+inside the backward's per-Gaussian kernel (gs_depth_backward_step) - without an autograd node for the pass.
+
 Outputs are the general path's bit for bit.  Not served: a colour image, `confidence` (the FSGS settings tuple), depth-limited
 lists, gradients to scales / rotations / a precomputed covariance.
 """
@@ -83,3 +86,42 @@ def depth_pass(settings, means3D, opacities, scales=None, rotations=None, cov3D_
             return _DepthPass.apply(means3D, opacities, None, settings, scales, rotations, cov3D_precomp, 0)
     return _DepthPass.apply(means3D if flags & 1 else means3D.detach(), opacities if flags & 2 else opacities.detach(),
                             means2D if flags & 1 else None, settings, scales, rotations, cov3D_precomp, flags)
+
+
+def depth_leg_step(settings, means3D, opacities, scales, rotations, grad, loss_fn, param, exp_avg, exp_avg_sq, lr, step,
+                   betas=(0.9, 0.999), eps=1e-15, cov3D_precomp=None):
+    """One DNGaussian depth leg as forward + loss + ONE fused backward-and-step (gs_depth_backward_step): the depth pass runs
+    without an autograd node, loss_fn(depth [1,H,W], alpha [1,H,W]) -> scalar is differentiated on its own small graph for the
+    two image cotangents, and the entry consumes them - the blend backward, then a per-Gaussian kernel that differentiates a
+    row and applies torch.optim.Adam's update at (lr, step) to it.  No gradient tensor of the leg's parameter exists.
+
+    grad "means":   param / exp_avg / exp_avg_sq [P,3]; param is the tensor the pass reads as means3D (stepped in place).
+    grad "opacity": param / moments [P,1] are the RAW opacity row and `opacities` its sigmoid, as the pass reads it.
+    The result equals depth_pass(...) -> loss.backward() -> [sigmoid backward] -> gs_adam_step on that one tensor bit for bit.
+    -> (loss (detached), radii)"""
+    from . import hip_backend
+    if grad not in ("means", "opacity"):
+        raise ValueError("depth_leg_step steps one tensor: grad is 'means' or 'opacity', not %r" % (grad,))
+    if hasattr(settings, "confidence"):
+        raise ValueError("depth_leg_step takes dgr_dng.GaussianRasterizationSettings: it does not rescale gradients by `confidence`")
+    const = isinstance(opacities, (int, float))
+    if const and grad == "opacity":
+        raise ValueError("a constant opacity has no gradient: grad='opacity' needs the activated opacity tensor")
+    if means3D.device.type != "cuda":
+        raise RuntimeError("gsplat depth pass got a tensor on %s - the rasterizer has no fallback path" % (means3D.device,))
+    if const:
+        opacities = _filled_opacity(means3D.device, means3D.shape[0], opacities)
+    rs = settings
+    backend = hip_backend()
+    with torch.no_grad():
+        det = lambda t: None if t is None else t.detach()   # noqa: E731
+        depth, alpha, radii, rec = backend.depth_forward(
+            means3D.detach(), opacities.detach(), det(scales), det(rotations), det(cov3D_precomp), rs.scale_modifier, rs.bg,
+            rs.viewmatrix, rs.projmatrix, rs.campos, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, rs.debug)
+    d, a = depth.requires_grad_(True), alpha.requires_grad_(True)
+    loss = loss_fn(d, a)
+    gd, ga = torch.autograd.grad(loss, (d, a), allow_unused=True)
+    if rec is not None and not (gd is None and ga is None):
+        with torch.no_grad():
+            backend.depth_backward_step(rec, gd, ga, 1 if grad == "means" else 2, param, exp_avg, exp_avg_sq, lr, step, betas, eps)
+    return loss.detach(), radii

@@ -152,11 +152,17 @@ class FsgsCriterion:
         loss, out, pout, branch = FusedFsgsLoss.apply(self, image, depth, gt_image, midas_depth, depth_weight)
         return loss, {"l1": out[5], "ssim": out[6], "base": out[1], "depth": pout[0], "r": pout[1], "branch": branch}
 
-    def __call__(self, image, depth, gt_image, midas_depth, depth_weight, pearson=None):
+    def photometric(self, image, gt_image, l1_weight=None):
+        """The photometric half on its own: l1_weight * L1 + lambda_dssim * (1 - SSIM) on the image as it is -> (base, L1, SSIM).
+        l1_weight None: FSGS's 1 - lambda_dssim; DNGaussian's loop (train_llff.py:154-155) weighs L1 by 1."""
         ops = self.ops
         Ll1 = ops.l1_loss(image, gt_image)
         ssim_value = ops.fused_ssim(image.unsqueeze(0), gt_image.unsqueeze(0))
-        base = (1.0 - self.lambda_dssim) * Ll1 + self.lambda_dssim * (1.0 - ssim_value)
+        w = (1.0 - self.lambda_dssim) if l1_weight is None else l1_weight
+        return w * Ll1 + self.lambda_dssim * (1.0 - ssim_value), Ll1, ssim_value
+
+    def __call__(self, image, depth, gt_image, midas_depth, depth_weight, pearson=None):
+        base, Ll1, ssim_value = self.photometric(image, gt_image)
         pearson = pearson or self.pearson
         if pearson is None:
             if not depth.is_cuda:

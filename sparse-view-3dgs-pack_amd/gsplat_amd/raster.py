@@ -926,9 +926,10 @@ class RasterBackend:
         return depth, alpha, radii, dict(view=f.view, g=g, keep=keep, radii=radii, geom=geom, img=img, binning=binning,
                                          R=int(num_rendered), P=P, W=W, H=H)
 
-    def depth_backward(self, rec, dL_ddepth, dL_dalpha, grad_flags):
+    def depth_backward(self, rec, dL_ddepth, dL_dalpha, grad_flags, workspace=None):
         """gs_depth_backward on the record of a depth_forward.  grad_flags: 1 means, 2 opacities, 3 both; a cotangent may be
-        None (zero).  -> (dL_dmeans3D [P,3], dL_dmeans2D [P,3], dL_dopacity [P,1]), None for what was not asked for."""
+        None (zero).  -> (dL_dmeans3D [P,3], dL_dmeans2D [P,3], dL_dopacity [P,1]), None for what was not asked for.
+        workspace: the caller's uint8 buffer (>= P * 128 rounded up to 256) - it keeps the float64 blend sums afterwards."""
         device = rec["radii"].device
         P, W, H, R = rec["P"], rec["W"], rec["H"], rec["R"]
         f32 = dict(dtype=torch.float32, device=device)
@@ -937,13 +938,39 @@ class RasterBackend:
         dm3 = torch.empty((P, 3), **f32) if grad_flags & 1 else None
         dm2 = torch.empty((P, 3), **f32) if grad_flags & 1 else None
         dop = torch.empty((P, 1), **f32) if grad_flags & 2 else None
-        ws = torch.empty((((P * 128 + 255) // 256) * 256,), dtype=torch.uint8, device=device)
+        ws = workspace
+        if ws is None:
+            ws = torch.empty((((P * 128 + 255) // 256) * 256,), dtype=torch.uint8, device=device)
         binning = rec["binning"]
         s = self._scratch(rec["geom"], rec["img"], binning, self._capacity_for(binning, P, W, H, R))
         self.api.call("depth_backward", C.byref(rec["view"]), C.byref(rec["g"]), rec["radii"].data_ptr(), C.byref(s), R,
                       _ptr(dL_ddepth), _ptr(dL_dalpha), int(grad_flags), _ptr(dm3), _ptr(dm2), _ptr(dop), ws.data_ptr(),
                       ws.numel(), self._stream(device))
         return dm3, dm2, dop
+
+    def depth_backward_step(self, rec, dL_ddepth, dL_dalpha, which, param, exp_avg, exp_avg_sq, lr, step, betas=(0.9, 0.999),
+                            eps=1e-15, flags=0, workspace=None):
+        """gs_depth_backward_step on the record of a depth_forward: the blend backward, then ONE per-Gaussian launch that
+        steps `param` (which 1: the means [P,3]; 2: the RAW opacities [P,1], the forward's `opacities` being their sigmoid)
+        and both moments in place with Adam at (lr, step).  No gradient tensor is made.
+        flags / workspace: capi.DEPTH_STEP_ROWS_GIVEN with the workspace a depth_backward call left."""
+        device = rec["radii"].device
+        P, W, H, R = rec["P"], rec["W"], rec["H"], rec["R"]
+        if not hasattr(self.api, "_depth_backward_step"):
+            raise RuntimeError("the loaded library has no gs_depth_backward_step - there is no fallback")
+        for name, t in (("param", param), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != P * (3 if which == 1 else 1):
+                raise RuntimeError("depth_backward_step: %s must be a contiguous fp32 tensor of %d rows on %s" % (name, P, device))
+        dL_ddepth, dL_dalpha = _prep(dL_ddepth, device), _prep(dL_dalpha, device)
+        ws = workspace
+        if ws is None:
+            ws = torch.empty((((P * 128 + 255) // 256) * 256,), dtype=torch.uint8, device=device)
+        binning = rec["binning"]
+        s = self._scratch(rec["geom"], rec["img"], binning, self._capacity_for(binning, P, W, H, R))
+        self.api.call("depth_backward_step", C.byref(rec["view"]), C.byref(rec["g"]), rec["radii"].data_ptr(), C.byref(s), R,
+                      _ptr(dL_ddepth), _ptr(dL_dalpha), int(which), param.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+                      float(lr), int(step), float(betas[0]), float(betas[1]), float(eps), int(flags), ws.data_ptr(), ws.numel(),
+                      self._stream(device))
 
     # ------------------------------------------------------------------ backward
     def rasterize_gaussians_backward(self, bg, means3D, radii, colors_precomp, opacities, scales, rotations,

@@ -2691,6 +2691,415 @@ class TrainerFSGS(Trainer):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# DNGaussian: DNGaussian/train_llff.py:68-228
+# ----------------------------------------------------------------------------------------------------------------
+class DngOptions(TrainOptions):
+    """DNGaussian/arguments/__init__.py:75-108 (OptimizationParams) over the fields of TrainOptions, and the constants
+    train_llff.py hard-codes as options, so that a test can compress the schedule."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.iterations = 30_000
+        self.position_lr_start = 0
+        self.opacity_lr = 0.05             # (position 0.00016, feature 0.0025, scaling 0.005, rotation 0.001: the model's own, LRS)
+        self.neural_grid = 5e-3
+        self.neural_net = 5e-4
+        self.error_tolerance = 0.2
+        self.split_opacity_thresh = 0.1
+        self.soft_depth_start = 1000
+        self.hard_depth_start = 0
+        self.shape_pena = 0.001
+        self.scale_pena = 0.001
+        self.opa_pena = 0.01
+        self.lambda_dssim = 0.2
+        self.densify_from_iter = 500
+        self.densify_until_iter = 15_000
+        self.densify_grad_threshold = 0.0001
+        self.min_opacity = 0.01            # prune_threshold
+        self.densify_rule = "dng"
+        self.patch_range = (5, 17)         # train_llff.py:64 ("LLFF")
+        self.smooth_start = 3000           # train_llff.py:106,132: `iteration > 3000`
+        self.near_prune_interval = 25      # train_llff.py:206
+        self.near_prune_start = 2000       # train_llff.py:209
+        self.clean_iterations = [6000, 1]  # train_llff.py:184: testing_iterations + [first_iter]
+        # True: the depth legs as forward + loss + ONE fused backward-and-step (gs_depth_backward_step) on a GPU model - the same
+        # bits as the un-fused legs, which are the arbiter.  Opt-in: at the LLFF size the measured gain (3-5 % of an iteration)
+        # is smaller than the window-to-window spread of the timing tool (profiles/dng_step_timing.txt, DESIGN.md section 4.12)
+        self.fused_depth_legs = False
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError("unknown option %s" % k)
+            setattr(self, k, v)
+
+
+def _settings_of(Settings, cam, bg_color, sh_degree, P, scaling_modifier=1.0, debug=False):
+    """The settings tuple of a DNGaussian pass; a tuple type with FSGS's `confidence` field gets the neutral one."""
+    kw = dict(image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
+              tanfovy=math.tan(cam.FoVy * 0.5), bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=cam.world_view_transform,
+              projmatrix=cam.full_proj_transform, sh_degree=sh_degree, campos=cam.camera_center, prefiltered=False, debug=debug)
+    if "confidence" in getattr(Settings, "_fields", ()):
+        kw["confidence"] = torch.ones((P, 1), dtype=torch.float32, device=cam.camera_center.device)
+    return Settings(**kw)
+
+
+def render_dng(viewpoint_camera, pc, neural, Rasterizer, Settings, bg_color, scaling_modifier=1.0, debug=False, view_dirs=None,
+               activations=None):
+    """= render() of DNGaussian/gaussian_renderer/__init__.py:21-123: colours from the neural renderer, the FSGS-generation
+    rasterizer with colors_precomp -> {render, depth, alpha, viewspace_points, visibility_filter, radii, opacity, color}; the
+    image is NOT clamped.
+    (sigma, colour) = neural(xyz, unit view directions); the opacity is sigmoid(_opacity): the reference's combine_opacity
+    returns the model's own opacity and ignores sigma, so sigma gets no gradient here and the first column of the sigma net's
+    last layer never learns.
+    view_dirs: (xyz, campos) -> unit directions [P,3]; default gsplat_amd.dng_reg.view_dirs (HIP tensors only).
+    activations: (scales, rotations, opacities) already formed by the caller, who also hands them to the regulariser."""
+    xyz = pc.get_xyz
+    screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True) + 0
+    try:
+        screenspace_points.retain_grad()
+    except Exception:
+        pass
+    if view_dirs is None:
+        from .dng_reg import view_dirs
+    dirs = view_dirs(xyz, viewpoint_camera.camera_center)
+    sigma, colour = neural(xyz, dirs)
+    scales, rotations, opacity = activations if activations is not None else (pc.get_scaling, pc.get_rotation, pc.get_opacity)
+    rs = _settings_of(Settings, viewpoint_camera, bg_color, pc.active_sh_degree, xyz.shape[0], scaling_modifier, debug)
+    image, radii, depth, alpha = Rasterizer(raster_settings=rs)(
+        means3D=xyz, means2D=screenspace_points, shs=None, colors_precomp=colour, opacities=opacity, scales=scales,
+        rotations=rotations, cov3D_precomp=None)
+    return {"render": image, "depth": depth, "alpha": alpha, "viewspace_points": screenspace_points,
+            "visibility_filter": radii > 0, "radii": radii, "opacity": opacity, "color": colour}
+
+
+class TrainerDNG(Trainer):
+    """The loop of DNGaussian/train_llff.py:68-228 in its order, one GPU: up to three optimizer steps per iteration.
+
+      hard leg   (iteration > hard_depth_start) depth-only pass at opacity 0.95, the depth regulariser, Adam on `xyz` ONLY;
+      soft leg   (iteration > soft_depth_start) the same loss on the pass at the model's opacities, Adam on `opacity` ONLY, on
+                 the means the hard leg has just stepped;
+      photometric  render_dng, L1 + lambda_dssim (1 - SSIM) + the per-Gaussian regulariser; clean / statistics / densification /
+                 near-camera prune; then Adam on xyz, opacity, scaling, rotation - unless one of those re-layouts ran, the
+                 near-camera prune with an empty mask included: the reference re-registers every per-Gaussian tensor there, the
+                 new tensors have no gradient and torch skips them - and on the neural renderer's six tensors, always.
+    Every tensor's bias corrections use its own step count (FlatAdam.seg_steps; torch keeps `step` per parameter): xyz and
+    opacity run ahead of scaling and rotation, the neural tensors ahead of those after re-layouts.
+    With DngOptions.fused_depth_legs = True a depth leg on a GPU model is forward + loss + gs_depth_backward_step
+    (depth_pass.depth_leg_step): the per-Gaussian tail steps the row it has differentiated, same bits; the default (False) is
+    pass -> backward -> FlatAdam.step on the one segment.
+
+    depth_mono: one [H,W] map per training camera as stored; the loss target 255 - depth_mono is formed once.
+    neural: nn.Module with forward(x, d) -> (sigma, colour) and get_params(lr, lr_net); default dng_neural.GridRenderer with
+      bound (max - min).max() / 2 * 1.2 and coord_center mean(xyz) of the model at construction (gaussian_model.py:197-200).
+    near_centers [K,3], near_range: the spiral render cameras' centres and --near.
+    depth_loss / regulariser / view_dirs / near_mask: the pieces without a CPU path as callables, for models that are not on
+      the GPU (defaults: gsplat_amd.depth_norm.depth_regulariser, dng_reg.gaussian_regulariser, dng_reg.view_dirs,
+      dng_reg.near_camera_mask).  Off the GPU the depth legs go through `Rasterizer` as the reference's render_for_depth /
+      render_for_opa do (colours of ones, the other inputs detached) and the neural tensors are stepped by torch's Adam.
+    Not carried: the SH rows are never stepped (no gradient reaches them in this loop), and the reference's `_features [P,32]`
+      and `_depth_err [P,1]` groups, which never get one either, do not exist here.
+    Closed: world_size > 1, with_nir models, trained exposure, alpha masks, depth limits, "sparse_adam", the two-phase side
+      launch, GraphedStep, and a fused photometric step (its colour and opacity gradients leave the rasterizer for the MLP and
+      the regulariser: Adam cannot sit in that tail)."""
+
+    after_backward = None   # parity instrument: callable(leg "hard" | "soft" | "photometric", trainer) behind an un-fused backward
+
+    def __init__(self, model, cameras, gt_images, depth_mono, neural=None, near_centers=None, near_range=0.0, bg=None,
+                 Rasterizer=None, Settings=None, criterion=None, depth_loss=None, regulariser=None, view_dirs=None, near_mask=None,
+                 opacity_lr=0.05, neural_lrs=(5e-3, 5e-4), lambda_dssim=0.2, depth_limit=None, fused_step=False, side_launch=False,
+                 **kw):
+        if Rasterizer is None or Settings is None:
+            import dgr_dng
+            Rasterizer = Rasterizer or dgr_dng.GaussianRasterizer
+            Settings = Settings or dgr_dng.GaussianRasterizationSettings
+        closed = None
+        if kw.get("world_size", 1) > 1:
+            closed = "data parallelism (world_size > 1)"
+        elif getattr(model, "with_nir", False):
+            closed = "a multispectral (with_nir) model"
+        elif getattr(model, "exposure", None) is not None:
+            closed = "a trained exposure"
+        elif kw.get("alpha_masks") is not None:
+            closed = "alpha masks"
+        elif depth_limit is not None:
+            closed = "depth-limited lists (depth_limit)"
+        elif kw.get("optimizer_type", "default") == "sparse_adam":
+            closed = 'optimizer_type = "sparse_adam"'
+        elif side_launch:
+            closed = "the two-phase side launch"
+        elif fused_step:
+            closed = "a fused photometric step"
+        if closed is not None:
+            raise RuntimeError("TrainerDNG: %s is closed to DNGaussian's trainer" % closed)
+        if not isinstance(model.optimizer, FlatAdam):
+            raise RuntimeError("TrainerDNG needs the flat Adam state (a model built with an api)")
+        if criterion is None:
+            from .fsgs_criterion import FsgsCriterion
+            from .losses import LossOps
+            criterion = FsgsCriterion(LossOps(model.optimizer.api), lambda_dssim=lambda_dssim)
+        dev = model.flat.device
+        bg = torch.zeros(3, dtype=torch.float32, device=dev) if bg is None else bg
+        super().__init__(model, cameras, gt_images, criterion, Rasterizer, Settings, bg, **kw)
+        if len(depth_mono) != len(cameras):
+            raise ValueError("TrainerDNG: one mono depth map per training camera")
+        self.mono = [(255.0 - torch.as_tensor(d, dtype=torch.float32).to(dev)).reshape(1, 1, *d.shape[-2:]) for d in depth_mono]
+        if neural is None:
+            from dng_neural import GridRenderer
+            with torch.no_grad():
+                xyz = model.params["xyz"].detach()
+                neural = GridRenderer(bound=float((xyz.max(0).values - xyz.min(0).values).max()) / 2 * 1.2,
+                                      coord_center=xyz.mean(0).cpu()).to(dev)
+        self.neural = neural
+        groups = neural.get_params(neural_lrs[0], neural_lrs[1])
+        if dev.type == "cuda":
+            from .optim import FusedAdam
+            self.neural_optimizer = FusedAdam(groups, lr=0.0, eps=1e-15, fuse_groups=True)
+        else:
+            self.neural_optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
+        self.near_centers = None if near_centers is None else torch.as_tensor(near_centers, dtype=torch.float32).reshape(-1, 3)
+        self.near_range = float(near_range)
+        self._depth_loss, self._regulariser, self._view_dirs, self._near_mask = depth_loss, regulariser, view_dirs, near_mask
+        model.optimizer.lr["opacity"] = opacity_lr   # DNGaussian/arguments/__init__.py:85 (the model's default is LGDWT-GS's)
+
+    @property
+    def depth_limit(self):
+        return None
+
+    @depth_limit.setter
+    def depth_limit(self, v):
+        if v is not None:
+            raise RuntimeError("TrainerDNG: depth-limited lists (depth_limit) are closed to DNGaussian's trainer")
+
+    def _fused_step_ok(self, backend, optimizer_step):
+        return False
+
+    def _fused_dp_ok(self, backend, optimizer_step):
+        return False
+
+    def neural_parameters(self):
+        return [p for g in self.neural_optimizer.param_groups for p in g["params"]]
+
+    def fused_legs_available(self):
+        """the model lives on the GPU and the loaded library has gs_depth_backward_step"""
+        m = self.model
+        return m.flat.is_cuda and hasattr(m.optimizer.api, "_depth_backward_step")
+
+    # -- the pieces
+    def _activations(self):
+        m = self.model
+        return m.get_scaling, m.get_rotation, m.get_opacity
+
+    def _render(self, cam, activations=None):
+        return render_dng(cam, self.model, self.neural, self.Rasterizer, self.Settings, self.bg, view_dirs=self._view_dirs,
+                          activations=activations)
+
+    def _depth_images(self, cam, kind):
+        """the un-fused leg's forward -> (depth [1,H,W], alpha): the depth-only pass on a GPU model, else the given Rasterizer
+        as render_for_depth / render_for_opa call it"""
+        m = self.model
+        xyz = m.params["xyz"]
+        scales, rotations = m.get_scaling.detach(), m.get_rotation.detach()
+        if xyz.is_cuda and "confidence" not in getattr(self.Settings, "_fields", ()):
+            from .depth_pass import depth_pass
+            rs = _settings_of(self.Settings, cam, self.bg, m.active_sh_degree, m.P)
+            if kind == "means":
+                depth, alpha, _ = depth_pass(rs, xyz, 0.95, scales, rotations, grad="means")
+            else:
+                depth, alpha, _ = depth_pass(rs, xyz.detach(), m.get_opacity, scales, rotations, grad="opacity")
+            return depth, alpha
+        rs = _settings_of(self.Settings, cam, self.bg, m.active_sh_degree, m.P)
+        ones = torch.ones((m.P, 3), dtype=torch.float32, device=xyz.device)
+        if kind == "means":
+            means, opacity = xyz, torch.ones((m.P, 1), dtype=torch.float32, device=xyz.device) * 0.95
+        else:
+            means, opacity = xyz.detach(), m.get_opacity
+        _, _, depth, alpha = self.Rasterizer(raster_settings=rs)(
+            means3D=means, means2D=torch.zeros_like(xyz, requires_grad=True), shs=None, colors_precomp=ones, opacities=opacity,
+            scales=scales, rotations=rotations, cov3D_precomp=None)
+        return depth, alpha
+
+    def _depth_leg(self, ci, kind, p_local, p_global, w_smooth, opt, stepping):
+        """one depth leg -> (loss, "fused" | "unfused"); Adam on `xyz` (kind "means") or `opacity` alone when `stepping`"""
+        m, o = self.model, self.model.optimizer
+        cam, mono = self.cameras[ci], self.mono[ci]
+        field = "xyz" if kind == "means" else "opacity"
+        others = tuple(name for name, _ in m.fields if name != field)
+        depth_loss = self._depth_loss
+        if depth_loss is None:
+            from .depth_norm import depth_regulariser as depth_loss
+
+        def loss_fn(depth, alpha):
+            return depth_loss(depth[None], mono, p_local, p_global, opt.error_tolerance, w_local=0.1, w_global=1.0,
+                              w_smooth=w_smooth)
+        m.zero_grad()
+        if stepping and opt.fused_depth_legs and self.fused_legs_available() and "confidence" not in getattr(self.Settings, "_fields", ()):
+            from .depth_pass import depth_leg_step
+            o.begin_step(others)
+            rs = _settings_of(self.Settings, cam, self.bg, m.active_sh_degree, m.P)
+            with torch.no_grad():
+                scales, rotations = m.get_scaling, m.get_rotation
+                opacity = 0.95 if kind == "means" else m.get_opacity
+            loss, _ = depth_leg_step(rs, m.params["xyz"].detach(), opacity, scales, rotations, kind, loss_fn,
+                                     m.params[field].detach(), o.field_views(o.exp_avg)[field], o.field_views(o.exp_avg_sq)[field],
+                                     o.lr[field], o.seg_steps[field], o.betas, o.eps)
+            o.invalidate_dormant()
+            return loss, "fused"
+        depth, alpha = self._depth_images(cam, kind)
+        loss = loss_fn(depth, alpha)
+        loss.backward()
+        if self.after_backward is not None:
+            self.after_backward("hard" if kind == "means" else "soft", self)
+        if stepping:
+            with torch.no_grad():
+                g = m.params[field].grad
+                view = m.grad_views()[field]
+                if g is None:
+                    view.zero_()
+                elif g.data_ptr() != view.data_ptr():
+                    view.copy_(g)
+                o.step(skip=others)
+        return loss.detach(), "unfused"
+
+    def prune_unseen(self, camera_indices=None, on_device=None, opt=None):
+        """clean_views (train_llff.py:264-274) through render_dng: forward only, `radii > 0` ORed on the device, prune_points
+        - a re-layout in the reference even when every Gaussian is seen"""
+        on_device = self._before_relayout(on_device, opt)
+        m = self.model
+        idx = range(len(self.cameras)) if camera_indices is None else list(camera_indices)
+        seen = torch.zeros((m.P,), dtype=torch.bool, device=m.flat.device)
+        with torch.no_grad():
+            for ci in idx:
+                seen |= self._render(self.cameras[ci])["radii"].reshape(-1) > 0
+        return m.prune_points(~seen, on_device=on_device)
+
+    def prune_near_cameras(self, centers, near_range, on_device=None, opt=None):
+        if self._near_mask is None:
+            return super().prune_near_cameras(centers, near_range, on_device=on_device, opt=opt)
+        on_device = self._before_relayout(on_device, opt)
+        with torch.no_grad():
+            xyz = self.model.params["xyz"].detach()
+            mask = self._near_mask(xyz, torch.as_tensor(centers, dtype=torch.float32).reshape(-1, 3).to(xyz.device), near_range)
+        return self.model.prune_points(mask.reshape(-1), on_device=on_device)
+
+    def train_iteration(self, iteration, opt):
+        """One iteration (1-based) of DNGaussian/train_llff.py:68-228 in its order: the learning rate of THIS iteration first
+        (update_learning_rate(max(iteration - position_lr_start, 0)): every step of iteration k uses the rate of k), the camera
+        draw, then by the same RNG the patch sizes of the legs that run (local, global; hard leg before soft leg), the hard leg,
+        the soft leg, the photometric leg, clean / statistics + densification / near-camera prune under no_grad, and the
+        photometric optimizer step - without the Gaussian groups when any of those re-layouts ran.
+        Returns dict(loss, loss_hard, loss_soft, camera, patches (hard local, hard global, soft local, soft global; None for a leg
+        that did not run), xyz_lr, stepped = dict(hard, soft, gaussians, neural), densified (DNGaussian's 4-tuple or None),
+        near_pruned (rows removed, or None when the prune did not run), cleaned (likewise), P, path = dict(hard, soft))."""
+        self.last_options = opt
+        m, o = self.model, self.model.optimizer
+        xyz_lr = m.update_learning_rate(max(iteration - opt.position_lr_start, 0), opt.position_lr_final, opt.position_lr_delay_mult,
+                                        opt.position_lr_max_steps)
+        o.lr["opacity"] = opt.opacity_lr
+        for g in self.neural_optimizer.param_groups:
+            g["lr"] = opt.neural_grid if g["name"] == "neural_encoder" else opt.neural_net
+        ci = self.draw_cameras(opt.seed)
+        cam = self.cameras[ci]
+        stepping = iteration < opt.iterations
+        w_smooth = 0.1 if iteration > opt.smooth_start else 0.0
+        lo, hi = opt.patch_range
+        patches = [None, None, None, None]
+        losses, path = dict(hard=None, soft=None), dict(hard=None, soft=None)
+        stepped = dict(hard=False, soft=False, gaussians=False, neural=False)
+        for k, (name, kind, start) in enumerate((("hard", "means", opt.hard_depth_start), ("soft", "opacity", opt.soft_depth_start))):
+            if iteration > start:
+                patches[2 * k] = self._rng.randint(lo, hi)
+                patches[2 * k + 1] = self._rng.randint(lo, hi)
+                losses[name], path[name] = self._depth_leg(ci, kind, patches[2 * k], patches[2 * k + 1], w_smooth, opt, stepping)
+                stepped[name] = stepping
+        # ---- photometric
+        m.zero_grad()
+        for p in self.neural_parameters():
+            p.grad = None
+        act = self._activations()
+        pkg = self._render(cam, act)
+        base, l1, ssim_value = self.criterion.photometric(pkg["render"], self.gts[ci], l1_weight=1.0)
+        regulariser = self._regulariser
+        if regulariser is None:
+            from .dng_reg import gaussian_regulariser as regulariser
+        loss = base + regulariser(act[0], pkg["opacity"], opt.shape_pena, opt.scale_pena, opt.opa_pena)
+        loss.backward()
+        if self.after_backward is not None:
+            self.after_backward("photometric", self)
+        self.last = dict(loss=loss.detach(), radii=pkg["radii"], parts=dict(l1=l1.detach(), ssim=ssim_value.detach()), path="unfused")
+        self.last_radii = pkg["radii"]
+        cleaned = densified = near_pruned = None
+        with torch.no_grad():
+            m.collect_grads()   # (into the flat gradient buffer, before anything replaces it; the SH rows: zeros, never stepped)
+            relayout = False
+            clean = iteration in opt.clean_iterations
+            if clean:
+                cleaned = self.prune_unseen(opt=opt)
+                relayout = True
+            if iteration < opt.densify_until_iter and not clean:
+                m.update_view_statistics(pkg["radii"], pkg["viewspace_points"].grad)
+                if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+                    gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
+                    densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
+                                                        opt.split_opacity_thresh, None, generator=gen,
+                                                        on_device=bool(opt.densify_on_device))
+                    relayout = True
+            if (iteration - 1) % opt.near_prune_interval == 0 and iteration > opt.near_prune_start:
+                # (prune_points runs in the reference even when the mask is empty - the default --near 0 makes it so - and
+                #  re-registers every tensor: a re-layout as far as the optimizer step below is concerned)
+                centers = self.near_centers if self.near_centers is not None else torch.zeros((0, 3))
+                near_pruned = self.prune_near_cameras(centers, self.near_range, opt=opt) if centers.shape[0] else 0
+                relayout = True
+            if stepping:
+                if not relayout:
+                    o.step(skip=("features",))
+                    stepped["gaussians"] = True
+                self.neural_optimizer.step()
+                stepped["neural"] = True
+            m.zero_grad()
+            for p in self.neural_parameters():
+                p.grad = None
+        return dict(loss=loss.detach(), loss_hard=losses["hard"], loss_soft=losses["soft"], camera=ci, patches=tuple(patches),
+                    xyz_lr=xyz_lr, stepped=stepped, densified=densified, near_pruned=near_pruned, cleaned=cleaned, P=m.P, path=path)
+
+    def checkpoint(self):
+        """Trainer.checkpoint() plus the neural renderer's state_dict, its optimizer state and the loop's RNG and camera stack"""
+        state = super().checkpoint()
+        state["neural"] = {k: v.detach().cpu().clone() for k, v in self.neural.state_dict().items()}
+        sd = self.neural_optimizer.state_dict()
+        state["neural_optimizer"] = dict(param_groups=sd["param_groups"], state={
+            k: {kk: (vv.detach().cpu().clone() if torch.is_tensor(vv) else vv) for kk, vv in v.items()} for k, v in sd["state"].items()})
+        state["rng"] = None if self._rng is None else self._rng.getstate()
+        state["stack"] = list(self._stack)
+        return state
+
+    def restore(self, state):
+        """the inverse of checkpoint(): model, moments and counters, neural renderer and its optimizer, RNG and camera stack"""
+        import random
+        self.model.restore(state)
+        self.neural.load_state_dict(state["neural"])
+        self.neural_optimizer.load_state_dict(state["neural_optimizer"])
+        if state.get("rng") is not None:
+            self._rng = random.Random()
+            self._rng.setstate(state["rng"])
+        self._stack = list(state["stack"])
+
+    def evaluate(self, cameras=None, gts=None, names=None, quantise=True, clamp=True, masks=None):
+        """PSNR / SSIM / L1 over a test set (default: the trainer's cameras and ground truth), every view rendered through
+        render_dng under no_grad -> gsplat_amd.evaluate.Evaluator.result(names).  No optimizer counter, statistic or random
+        stream is touched."""
+        from .evaluate import Evaluator
+        cameras = self.cameras if cameras is None else cameras
+        gts = self.gts if gts is None else gts
+        ev = None
+        with torch.no_grad():
+            for i, (cam, gt) in enumerate(zip(cameras, gts)):
+                img = self._render(cam)["render"]
+                if ev is None:
+                    ev = Evaluator(len(cameras), img.shape[0], img.shape[1], img.shape[2], img.device)
+                ev.add(i, img, gt, mask=None if masks is None else masks[i], clamp=clamp, quantise=quantise)
+        return ev.result(names)
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # hipGraph replay of the steady-state single-GPU step
 # ----------------------------------------------------------------------------------------------------------------
 def _status_check(tag, num_rendered, overflow, trunc_failed):
@@ -2724,6 +3133,8 @@ class GraphedStep:
         settle); every later camera takes one."""
         if isinstance(trainer, TrainerFSGS):
             raise RuntimeError("GraphedStep (hipGraph replay) is closed to the FSGS rasterizer generation's trainer")
+        if isinstance(trainer, TrainerDNG):
+            raise RuntimeError("GraphedStep (hipGraph replay) is closed to DNGaussian's trainer")
         self.tr = trainer
         trainer._graphed = self   # Trainer.sync() settles the last replay too
         self.fixed_capacity = capacity
