@@ -733,6 +733,39 @@ int gs_view_dirs_bwd(const float* xyz, const float* campos, int64_t P, const flo
                      void* stream);
 int gs_near_mask(const float* xyz, int64_t P, const float* centers, int32_t K, float near, uint8_t* mask /*[P]*/, void* stream);
 
+/* ---- what DNGaussian's DTU loop adds: object mask, masked-mean fill, alpha penalty, colour rules (csrc/gs_dng_dtu.hip) ----
+ * Additive entries (GS_ABI_VERSION unchanged).  fp32 images of n = H W elements, 1 <= n < 2^31; masks are one byte per element,
+ * 0 / non-zero.  Every count stays in device memory; no atomics, no host synchronisation, the same bits on every run.
+ * gs_dtu_mask: gt [3,H,W]; dark = every channel < thr (fp32, strictly); mask[y,x] = 1 iff the run of dark pixels ending at (y,x)
+ *   going up its column is at least min(y + 1, run) long (run >= 1; train_dtu.py:84-94 has run = 50).  count[0] (int32) = masked
+ *   pixels; gt_out [3,H,W] = gt with the masked pixels 0 in every channel, and may be gt itself.  One launch, one workgroup.
+ * gs_masked_fill_fwd: out = x where mask == 0, else mean of x over mask == 0: the float64 sum of per-workgroup partials, added
+ *   in index order, over the float64 count, rounded to fp32 once (no unmasked element: NaN).  mean_out [1], nullable, receives
+ *   it too.  tmp: >= gs_masked_tmp_bytes(n) bytes of device scratch.  Two launches.  gs_masked_fill_bwd: g_x = g where
+ *   mask == 0, +0.0 where masked (nothing flows through the mean).  One launch.
+ * gs_alpha_penalty_fwd: out[0] = mean of alpha^2 over mask != 0, squares and sum in float64 in the same fixed order, rounded
+ *   once; an empty mask gives NaN.  Two launches; tmp (gs_masked_tmp_bytes(n)) keeps the count for the backward of the SAME
+ *   arguments.  gs_alpha_penalty_bwd: g [1] from device memory; g_alpha = (g / (float)count) * (2 * alpha) in fp32 where masked,
+ *   +0.0 elsewhere; count 0: +0.0 everywhere.  One launch.
+ * gs_dng_colour_rule (train_dtu.py:218-230): colour [P,3] read-only, stat [P] and opacity [P] (the raw row) edited in place.  The
+ *   black rule fires on a row when max_c < black_thr, the white rule when min_c > white_thr (strict, fp32; a NaN colour fires
+ *   neither); a rule that fires divides stat by its divisor in fp32 and, if its reset flag is set, stores `value` into opacity.
+ *   Black is applied before white; *_on = 0 switches a rule off.  counts[2] (int32) = rows the black / the white rule fired on.
+ *   One launch.
+ * GS_E_NULL: a required pointer is missing; GS_E_SHAPE: H, W, run or P < 1, or n / P >= 2^31. */
+int gs_dtu_mask(const float* gt, int32_t H, int32_t W, float thr, int32_t run, uint8_t* mask /*[H,W]*/, int32_t* count /*[1]*/,
+                float* gt_out /*[3,H,W]*/, void* stream);
+size_t gs_masked_tmp_bytes(int64_t n);
+int gs_masked_fill_fwd(const float* x, const uint8_t* mask, int64_t n, void* tmp, float* out /*[n]*/, float* mean_out /*[1]*/,
+                       void* stream);
+int gs_masked_fill_bwd(const float* g, const uint8_t* mask, int64_t n, float* g_x /*[n]*/, void* stream);
+int gs_alpha_penalty_fwd(const float* alpha, const uint8_t* mask, int64_t n, void* tmp, float* out /*[1]*/, void* stream);
+int gs_alpha_penalty_bwd(const float* alpha, const uint8_t* mask, int64_t n, const void* tmp, const float* g /*[1]*/,
+                         float* g_alpha /*[n]*/, void* stream);
+int gs_dng_colour_rule(const float* colour, float* stat, float* opacity, int64_t P, int32_t black_on, float black_thr,
+                       float black_div, int32_t black_reset, int32_t white_on, float white_thr, float white_div,
+                       int32_t white_reset, float value, int32_t* counts /*[2]*/, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

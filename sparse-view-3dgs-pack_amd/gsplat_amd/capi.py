@@ -206,6 +206,13 @@ PROTOTYPES = {
     "view_dirs_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "view_dirs_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P]),
     "near_mask": (C.c_int, [_P, _I64, _P, _I32, _F, _P, _P]),
+    "dtu_mask": (C.c_int, [_P, _I32, _I32, _F, _I32, _P, _P, _P, _P]),
+    "masked_tmp_bytes": (_SZ, [_I64]),
+    "masked_fill_fwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
+    "masked_fill_bwd": (C.c_int, [_P, _P, _I64, _P, _P]),
+    "alpha_penalty_fwd": (C.c_int, [_P, _P, _I64, _P, _P, _P]),
+    "alpha_penalty_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
+    "dng_colour_rule": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _F, _I32, _I32, _F, _F, _I32, _F, _P, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -301,6 +308,10 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                "dng_heads_tmp_bytes", "dng_heads_fwd", "dng_heads_bwd",
                # DNGaussian's per-Gaussian regulariser, view directions, near mask: restated in torch (tests/dng_reg_reference.py)
                "dng_reg_tmp_bytes", "dng_reg_fwd", "dng_reg_bwd", "view_dirs_fwd", "view_dirs_bwd", "near_mask",
+               # what DNGaussian's DTU loop adds (mask, masked-mean fill, alpha penalty, colour rules): restated in torch
+               # (tests/dtu_reference.py)
+               "dtu_mask", "masked_tmp_bytes", "masked_fill_fwd", "masked_fill_bwd", "alpha_penalty_fwd", "alpha_penalty_bwd",
+               "dng_colour_rule",
                # densify / split / prune on the device: GaussianModelLite.densify_and_prune's host path is the arbiter
                # (tests/densify_reference.py restates the plan in torch)
                "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather",

@@ -2917,21 +2917,31 @@ class TrainerDNG(Trainer):
             scales=scales, rotations=rotations, cov3D_precomp=None)
         return depth, alpha
 
-    def _depth_leg(self, ci, kind, p_local, p_global, w_smooth, opt, stepping):
-        """one depth leg -> (loss, "fused" | "unfused"); Adam on `xyz` (kind "means") or `opacity` alone when `stepping`"""
-        m, o = self.model, self.model.optimizer
-        cam, mono = self.cameras[ci], self.mono[ci]
-        field = "xyz" if kind == "means" else "opacity"
-        others = tuple(name for name, _ in m.fields if name != field)
+    def _leg_loss(self, ci, leg, depth, alpha, p_local, p_global, w_smooth, opt):
+        """the loss of leg "hard" | "soft" on the pass's depth [1,H,W] and alpha images"""
         depth_loss = self._depth_loss
         if depth_loss is None:
             from .depth_norm import depth_regulariser as depth_loss
+        return depth_loss(depth[None], self.mono[ci], p_local, p_global, opt.error_tolerance, w_local=0.1, w_global=1.0,
+                          w_smooth=w_smooth)
+
+    def _depth_leg(self, ci, kind, p_local, p_global, w_smooth, opt, stepping, leg=None, keep_grads=False, step_fields=None):
+        """one depth leg -> (loss, "fused" | "unfused"); Adam on `xyz` (kind "means") or `opacity` alone when `stepping`.
+        leg: the name _leg_loss and after_backward get (default "hard" / "soft" by kind).  keep_grads: the gradients an earlier
+        leg left are not cleared, this leg's add to them (un-fused only); step_fields: the fields the un-fused step takes
+        (default: this leg's one)."""
+        m, o = self.model, self.model.optimizer
+        cam = self.cameras[ci]
+        field = "xyz" if kind == "means" else "opacity"
+        leg = leg or ("hard" if kind == "means" else "soft")
+        step_fields = (field,) if step_fields is None else tuple(step_fields)
+        others = tuple(name for name, _ in m.fields if name not in step_fields)
 
         def loss_fn(depth, alpha):
-            return depth_loss(depth[None], mono, p_local, p_global, opt.error_tolerance, w_local=0.1, w_global=1.0,
-                              w_smooth=w_smooth)
-        m.zero_grad()
-        if stepping and opt.fused_depth_legs and self.fused_legs_available() and "confidence" not in getattr(self.Settings, "_fields", ()):
+            return self._leg_loss(ci, leg, depth, alpha, p_local, p_global, w_smooth, opt)
+        if not keep_grads:
+            m.zero_grad()
+        if stepping and not keep_grads and step_fields == (field,) and opt.fused_depth_legs and self.fused_legs_available() and "confidence" not in getattr(self.Settings, "_fields", ()):
             from .depth_pass import depth_leg_step
             o.begin_step(others)
             rs = _settings_of(self.Settings, cam, self.bg, m.active_sh_degree, m.P)
@@ -2947,15 +2957,16 @@ class TrainerDNG(Trainer):
         loss = loss_fn(depth, alpha)
         loss.backward()
         if self.after_backward is not None:
-            self.after_backward("hard" if kind == "means" else "soft", self)
+            self.after_backward(leg, self)
         if stepping:
             with torch.no_grad():
-                g = m.params[field].grad
-                view = m.grad_views()[field]
-                if g is None:
-                    view.zero_()
-                elif g.data_ptr() != view.data_ptr():
-                    view.copy_(g)
+                views = m.grad_views()
+                for name in step_fields:
+                    g, view = m.params[name].grad, views[name]
+                    if g is None:
+                        view.zero_()
+                    elif g.data_ptr() != view.data_ptr():
+                        view.copy_(g)
                 o.step(skip=others)
         return loss.detach(), "unfused"
 
@@ -2990,14 +3001,9 @@ class TrainerDNG(Trainer):
         that did not run), xyz_lr, stepped = dict(hard, soft, gaussians, neural), densified (DNGaussian's 4-tuple or None),
         near_pruned (rows removed, or None when the prune did not run), cleaned (likewise), P, path = dict(hard, soft))."""
         self.last_options = opt
-        m, o = self.model, self.model.optimizer
-        xyz_lr = m.update_learning_rate(max(iteration - opt.position_lr_start, 0), opt.position_lr_final, opt.position_lr_delay_mult,
-                                        opt.position_lr_max_steps)
-        o.lr["opacity"] = opt.opacity_lr
-        for g in self.neural_optimizer.param_groups:
-            g["lr"] = opt.neural_grid if g["name"] == "neural_encoder" else opt.neural_net
+        m = self.model
+        xyz_lr = self._set_rates(iteration, opt)
         ci = self.draw_cameras(opt.seed)
-        cam = self.cameras[ci]
         stepping = iteration < opt.iterations
         w_smooth = 0.1 if iteration > opt.smooth_start else 0.0
         lo, hi = opt.patch_range
@@ -3010,12 +3016,29 @@ class TrainerDNG(Trainer):
                 patches[2 * k + 1] = self._rng.randint(lo, hi)
                 losses[name], path[name] = self._depth_leg(ci, kind, patches[2 * k], patches[2 * k + 1], w_smooth, opt, stepping)
                 stepped[name] = stepping
-        # ---- photometric
+        pkg, loss = self._photometric_leg(ci, opt)
+        cleaned, densified, near_pruned = self._after_photometric(iteration, opt, pkg, stepping, stepped)
+        return dict(loss=loss.detach(), loss_hard=losses["hard"], loss_soft=losses["soft"], camera=ci, patches=tuple(patches),
+                    xyz_lr=xyz_lr, stepped=stepped, densified=densified, near_pruned=near_pruned, cleaned=cleaned, P=m.P, path=path)
+
+    def _set_rates(self, iteration, opt):
+        """the learning rates of THIS iteration -> the means' rate"""
+        m, o = self.model, self.model.optimizer
+        xyz_lr = m.update_learning_rate(max(iteration - opt.position_lr_start, 0), opt.position_lr_final, opt.position_lr_delay_mult,
+                                        opt.position_lr_max_steps)
+        o.lr["opacity"] = opt.opacity_lr
+        for g in self.neural_optimizer.param_groups:
+            g["lr"] = opt.neural_grid if g["name"] == "neural_encoder" else opt.neural_net
+        return xyz_lr
+
+    def _photometric_leg(self, ci, opt):
+        """render_dng, L1 + lambda_dssim (1 - SSIM) + the per-Gaussian regulariser, backward -> (pkg, loss)"""
+        m = self.model
         m.zero_grad()
         for p in self.neural_parameters():
             p.grad = None
         act = self._activations()
-        pkg = self._render(cam, act)
+        pkg = self._render(self.cameras[ci], act)
         base, l1, ssim_value = self.criterion.photometric(pkg["render"], self.gts[ci], l1_weight=1.0)
         regulariser = self._regulariser
         if regulariser is None:
@@ -3026,6 +3049,18 @@ class TrainerDNG(Trainer):
             self.after_backward("photometric", self)
         self.last = dict(loss=loss.detach(), radii=pkg["radii"], parts=dict(l1=l1.detach(), ssim=ssim_value.detach()), path="unfused")
         self.last_radii = pkg["radii"]
+        return pkg, loss
+
+    def _near_prune_due(self, iteration, opt):
+        return (iteration - 1) % opt.near_prune_interval == 0 and iteration > opt.near_prune_start
+
+    def _before_densify(self, iteration, opt, pkg):
+        """behind the statistics of a densifying iteration, in front of densify_and_prune_dng (under no_grad)"""
+
+    def _after_photometric(self, iteration, opt, pkg, stepping, stepped):
+        """clean / statistics + densification / near-camera prune under no_grad, then the photometric optimizer step - without the
+        Gaussian groups when any of those re-layouts ran -> (cleaned, densified, near_pruned)"""
+        m, o = self.model, self.model.optimizer
         cleaned = densified = near_pruned = None
         with torch.no_grad():
             m.collect_grads()   # (into the flat gradient buffer, before anything replaces it; the SH rows: zeros, never stepped)
@@ -3037,12 +3072,13 @@ class TrainerDNG(Trainer):
             if iteration < opt.densify_until_iter and not clean:
                 m.update_view_statistics(pkg["radii"], pkg["viewspace_points"].grad)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+                    self._before_densify(iteration, opt, pkg)
                     gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
                     densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
                                                         opt.split_opacity_thresh, None, generator=gen,
                                                         on_device=bool(opt.densify_on_device))
                     relayout = True
-            if (iteration - 1) % opt.near_prune_interval == 0 and iteration > opt.near_prune_start:
+            if self._near_prune_due(iteration, opt):
                 # (prune_points runs in the reference even when the mask is empty - the default --near 0 makes it so - and
                 #  re-registers every tensor: a re-layout as far as the optimizer step below is concerned)
                 centers = self.near_centers if self.near_centers is not None else torch.zeros((0, 3))
@@ -3057,8 +3093,7 @@ class TrainerDNG(Trainer):
             m.zero_grad()
             for p in self.neural_parameters():
                 p.grad = None
-        return dict(loss=loss.detach(), loss_hard=losses["hard"], loss_soft=losses["soft"], camera=ci, patches=tuple(patches),
-                    xyz_lr=xyz_lr, stepped=stepped, densified=densified, near_pruned=near_pruned, cleaned=cleaned, P=m.P, path=path)
+        return cleaned, densified, near_pruned
 
     def checkpoint(self):
         """Trainer.checkpoint() plus the neural renderer's state_dict, its optimizer state and the loop's RNG and camera stack"""
@@ -3097,6 +3132,179 @@ class TrainerDNG(Trainer):
                     ev = Evaluator(len(cameras), img.shape[0], img.shape[1], img.shape[2], img.device)
                 ev.add(i, img, gt, mask=None if masks is None else masks[i], clamp=clamp, quantise=quantise)
         return ev.result(names)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# DNGaussian on DTU: DNGaussian/train_dtu.py:39-250
+# ----------------------------------------------------------------------------------------------------------------
+class DngDtuOptions(DngOptions):
+    """DngOptions with what train_dtu.py hard-codes: the patch range, no smoothness term, no near-camera prune, the object
+    mask's threshold and run, the soft leg's gate on the running hard loss, the alpha leg, and the two colour rules.
+    A rule is (threshold, divisor, reset) or None; reset is False, True (every time the rule runs) or a period n (the
+    iterations with iteration % n == 0)."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.patch_range = (17, 53)                 # train_dtu.py:62
+        self.smooth_start = None                    # no smoothness term at any iteration
+        self.near_prune_interval = None             # no spiral cameras, no near-camera prune
+        self.near_prune_start = None
+        self.bg_threshold = 30 / 255                # :87 (scan110: 15 / 255, :89)
+        self.bg_run = 50                            # :91: the pixel and the 49 above it
+        self.soft_gate = 0.1                        # :128
+        self.ema = (0.1, 0.9)                       # :127
+        self.alpha_leg = True                       # :155-159
+        self.black_rule = (20 / 255, 10, True)      # :221-223
+        self.white_rule = (240 / 255, 2, 2001)      # :226-230
+        self.reset_opacity_to = 0.1                 # :223, :230
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError("unknown option %s" % k)
+            setattr(self, k, v)
+
+    @classmethod
+    def for_scan(cls, name, **kw):
+        """the reference's three scan exceptions (it tests `'scan110' in source_path` and so on): scan110 has the lower mask
+        threshold and no colour rule, scan114 and scan21 no white rule"""
+        name = str(name)
+        o = dict()
+        if "scan110" in name:
+            o.update(bg_threshold=15 / 255, black_rule=None, white_rule=None)
+        elif "scan114" in name or "scan21" in name:
+            o.update(white_rule=None)
+        o.update(kw)
+        return cls(**o)
+
+
+def _rule_at(rule, iteration):
+    """a DngDtuOptions rule at an iteration -> (threshold, divisor, reset now) or None"""
+    if rule is None:
+        return None
+    thr, div, reset = rule
+    return thr, div, bool(reset) and iteration % int(reset) == 0
+
+
+class TrainerDNGDTU(TrainerDNG):
+    """The loop of DNGaussian/train_dtu.py:39-250 in its order - TrainerDNG's with what the DTU script adds:
+
+      mask       per camera, once (:84-94; it depends on the ground truth alone): the object mask, the ground truth with the
+                 masked pixels zeroed (what the photometric leg sees), and the mono target 255 - depth_mono FILLED with the
+                 mean of its unmasked pixels (:104, :137);
+      hard leg   as TrainerDNG's on the depth image filled the same way (:105), no smoothness term; then
+                 ema_loss_hard = 0.1 loss_hard + 0.9 ema_loss_hard, a Python float: 4 bytes read back, the loop's ONE
+                 synchronisation - it decides host work;
+      soft leg   iff iteration > soft_depth_start AND ema_loss_hard < soft_gate (:128); its patch sizes are drawn only then;
+      alpha leg  every iteration (:155-159): the soft pass again, mean(alpha[mask] ** 2), Adam on `opacity` alone - with an
+                 empty mask a NaN loss and a zero gradient that Adam still steps on;
+      photometric  against the zeroed ground truth; in front of every densification the colour rules (:218-230) on the
+                 per-Gaussian colour of THIS iteration's photometric render (nothing has been stepped since: the reference's
+                 second render gives the same tensor); no near-camera prune.
+    The last iteration (iteration == opt.iterations): the reference leaves out every step but the alpha leg's, and does not
+    clear the gradients in between - so that one step takes `xyz` with the hard leg's gradient and `opacity` with the soft
+    leg's plus the alpha leg's.  The same here (un-fused: no fused form steps two tensors).
+    With DngDtuOptions.fused_depth_legs = True all three legs go through depth_pass.depth_leg_step on a GPU model.
+
+    background_mask / masked_fill / alpha_penalty / colour_rule: the new pieces as callables for models that are not on the GPU
+      (defaults: gsplat_amd.dng_dtu's).  opt: the DngDtuOptions whose bg_threshold / bg_run form the masks (default: its
+      defaults).  self.gts holds the ZEROED images: evaluate() compares against them unless given others.
+    train_iteration's dict gains loss_alpha, ema_loss_hard, soft_gate_open, rule_counts ((black, white) device counts of a
+      densifying iteration, else None), stepped["alpha"], path["alpha"].  Everything closed to TrainerDNG is closed here."""
+
+    def __init__(self, model, cameras, gt_images, depth_mono, opt=None, background_mask=None, masked_fill=None, alpha_penalty=None,
+                 colour_rule=None, **kw):
+        super().__init__(model, cameras, gt_images, depth_mono, **kw)
+        opt = DngDtuOptions() if opt is None else opt
+        if background_mask is None or masked_fill is None or alpha_penalty is None or colour_rule is None:
+            from . import dng_dtu
+            background_mask = background_mask or dng_dtu.dtu_background_mask
+            masked_fill = masked_fill or dng_dtu.masked_mean_fill
+            alpha_penalty = alpha_penalty or dng_dtu.alpha_penalty
+            colour_rule = colour_rule or dng_dtu.colour_rule
+        self._masked_fill, self._alpha_penalty, self._colour_rule = masked_fill, alpha_penalty, colour_rule
+        dev = model.flat.device
+        self.bg_masks, gts, mono = [], [], []
+        with torch.no_grad():
+            for gt, mn in zip(self.gts, self.mono):
+                mask, zeroed = background_mask(torch.as_tensor(gt, dtype=torch.float32).to(dev).contiguous(), opt.bg_threshold,
+                                               opt.bg_run)
+                self.bg_masks.append(mask)
+                gts.append(zeroed)
+                mono.append(masked_fill(mn.reshape(mask.shape), mask).reshape(mn.shape))
+        self.gts, self.mono = gts, mono
+        self.ema_loss_hard = 0.0
+        from .dng_dtu import reset_value
+        self._reset_value = reset_value
+
+    def _leg_loss(self, ci, leg, depth, alpha, p_local, p_global, w_smooth, opt):
+        if leg == "alpha":
+            return self._alpha_penalty(alpha, self.bg_masks[ci])
+        return super()._leg_loss(ci, leg, self._masked_fill(depth, self.bg_masks[ci]), alpha, p_local, p_global, w_smooth, opt)
+
+    def _near_prune_due(self, iteration, opt):
+        return False
+
+    def _before_densify(self, iteration, opt, pkg):
+        black, white = _rule_at(opt.black_rule, iteration), _rule_at(opt.white_rule, iteration)
+        self._rule_counts = None
+        if black is None and white is None:
+            return
+        m = self.model
+        self._rule_counts = self._colour_rule(pkg["color"].detach(), m.xyz_gradient_accum, m.params["opacity"].detach(),
+                                              black=black, white=white, value=self._reset_value(opt.reset_opacity_to))
+
+    def train_iteration(self, iteration, opt):
+        """One iteration (1-based) of train_dtu.py:64-247 in its order: learning rate, camera draw, hard leg, the `ema`
+        read-back, soft leg if the gate is open, alpha leg, photometric leg against the zeroed ground truth, clean / statistics /
+        colour rules + densification, photometric step under TrainerDNG's re-layout rule.  The patch sizes of a leg are drawn
+        only when it runs, by the loop's one RNG, hard before soft.
+        Returns TrainerDNG's dict (near_pruned: always None) plus loss_alpha, ema_loss_hard, soft_gate_open (None while the
+        soft leg is before its start), rule_counts, stepped["alpha"], path["alpha"]."""
+        self.last_options = opt
+        m = self.model
+        xyz_lr = self._set_rates(iteration, opt)
+        ci = self.draw_cameras(opt.seed)
+        stepping = iteration < opt.iterations
+        last = not stepping
+        lo, hi = opt.patch_range
+        patches = [None, None, None, None]
+        losses, path = dict(hard=None, soft=None, alpha=None), dict(hard=None, soft=None, alpha=None)
+        stepped = dict(hard=False, soft=False, alpha=False, gaussians=False, neural=False)
+        kept = False    # the last iteration: a leg that ran left its gradient behind
+        if iteration > opt.hard_depth_start:
+            patches[0], patches[1] = self._rng.randint(lo, hi), self._rng.randint(lo, hi)
+            losses["hard"], path["hard"] = self._depth_leg(ci, "means", patches[0], patches[1], 0.0, opt, stepping)
+            stepped["hard"] = stepping
+            kept = last
+            self.ema_loss_hard = opt.ema[0] * float(losses["hard"]) + opt.ema[1] * self.ema_loss_hard   # (the read-back)
+        gate = None
+        if iteration > opt.soft_depth_start:
+            gate = self.ema_loss_hard < opt.soft_gate
+            if gate:
+                patches[2], patches[3] = self._rng.randint(lo, hi), self._rng.randint(lo, hi)
+                losses["soft"], path["soft"] = self._depth_leg(ci, "opacity", patches[2], patches[3], 0.0, opt, stepping,
+                                                               keep_grads=kept)
+                stepped["soft"] = stepping
+                kept = last
+        if opt.alpha_leg:
+            fields = ("opacity",) if not (last and losses["hard"] is not None) else ("xyz", "opacity")
+            losses["alpha"], path["alpha"] = self._depth_leg(ci, "opacity", None, None, 0.0, opt, True, leg="alpha",
+                                                             keep_grads=kept, step_fields=fields)
+            stepped["alpha"] = True
+        self._rule_counts = None
+        pkg, loss = self._photometric_leg(ci, opt)
+        cleaned, densified, _ = self._after_photometric(iteration, opt, pkg, stepping, stepped)
+        return dict(loss=loss.detach(), loss_hard=losses["hard"], loss_soft=losses["soft"], loss_alpha=losses["alpha"], camera=ci,
+                    patches=tuple(patches), xyz_lr=xyz_lr, stepped=stepped, densified=densified, near_pruned=None, cleaned=cleaned,
+                    P=m.P, path=path, ema_loss_hard=self.ema_loss_hard, soft_gate_open=gate, rule_counts=self._rule_counts)
+
+    def checkpoint(self):
+        state = super().checkpoint()
+        state["ema_loss_hard"] = float(self.ema_loss_hard)
+        return state
+
+    def restore(self, state):
+        super().restore(state)
+        self.ema_loss_hard = float(state.get("ema_loss_hard", 0.0))
 
 
 # ----------------------------------------------------------------------------------------------------------------
