@@ -766,6 +766,36 @@ int gs_dng_colour_rule(const float* colour, float* stat, float* opacity, int64_t
                        float black_div, int32_t black_reset, int32_t white_on, float white_thr, float white_div,
                        int32_t white_reset, float value, int32_t* counts /*[2]*/, void* stream);
 
+/* ---- what DNGaussian's Blender loops add for a white background: target and white rules (csrc/gs_dng_blender.hip) ----
+ * Additive entries (GS_ABI_VERSION unchanged).  Every count stays in device memory; no floating-point atomics, no host
+ * synchronisation, the same bits on every run.  1 <= H W < 2^31, 1 <= P < 2^31.
+ * gs_blender_target (train_blender.py:87, :96-97): gt [3,H,W]; mask[y,x] = 1 iff the minimum over the three channels > thr
+ *   (fp32, strictly; a NaN channel leaves the pixel unmasked).  target [H,W], nullable, = +0.0 where masked, else
+ *   255.0f - mono (one fp32 subtraction); mono [H,W] is required only with target.  count[0] (int32) = masked pixels, from
+ *   per-workgroup partials in tmp (>= gs_blender_tmp_bytes(H W) bytes of device scratch).  Two launches.  The outputs alias no
+ *   input.
+ * gs_dng_white_rule (:207-211): colour [P,3] read-only, stat [P] and opacity [P] (the raw row) edited in place.  A row fires iff
+ *   min_c colour > thr (strict, fp32; a NaN fires nothing); it gets stat = +0.0 and opacity = log(x / (1 - x)) with
+ *   x = factor * sigmoid(opacity), evaluated in double from the fp32 input and rounded once (-inf gives -inf, NaN gives NaN).
+ *   counts[0] (int32) = rows that fired.  One kernel launch behind a 4-byte hipMemsetAsync of counts on the same stream: every
+ *   workgroup adds its count with one INTEGER atomic add (order-free); there is no floating-point atomic.
+ * gs_dng_white_rule_sh (:366-370): the same rule on colour = max(eval_sh(active_degree, rows, dir) + 0.5, 0),
+ *   dir = (xyz - campos) normalised, evaluated in double from the fp32 inputs and rounded once (a zero-length direction: NaN
+ *   colours, nothing fires - from degree 1 on; degree 0 does not use the direction).  The rows of M = 1, 4, 9 or 16 coefficients come split - dc [P,1,3] and rows = rest [P,M-1,3]
+ *   (ignored when M == 1) - or packed: dc null and rows [P,M,3].  Coefficients above the active degree are not read.
+ *   colour_out [P,3], nullable, receives the colour.  Counted and launched as gs_dng_white_rule.
+ * GS_E_NULL: a required pointer is missing; GS_E_SHAPE: H, W or P < 1, H W or P >= 2^31, M not 1 / 4 / 9 / 16, active_degree < 0 or > 3
+ *   or (active_degree + 1)^2 > M.  Every check precedes the first launch.  A failed memset
+ *   returns its hipError_t (> 0), as a failed launch does. */
+size_t gs_blender_tmp_bytes(int64_t n);
+int gs_blender_target(const float* gt, const float* mono, int32_t H, int32_t W, float thr, void* tmp, uint8_t* mask /*[H,W]*/,
+                      int32_t* count /*[1]*/, float* target /*[H,W]*/, void* stream);
+int gs_dng_white_rule(const float* colour, float* stat, float* opacity, int64_t P, float thr, float factor, int32_t* counts /*[1]*/,
+                      void* stream);
+int gs_dng_white_rule_sh(const float* xyz, const float* dc, const float* rows, int32_t M, int32_t active_degree, const float* campos,
+                         float* stat, float* opacity, int64_t P, float thr, float factor, float* colour_out /*[P,3]*/,
+                         int32_t* counts /*[1]*/, void* stream);
+
 /* ---- losses (images are [C,H,W] or [N,C,H,W] contiguous fp32) ---- */
 
 /* sums[0] = sum |a-b| over n elements (atomically added: zero it first).

@@ -213,6 +213,10 @@ PROTOTYPES = {
     "alpha_penalty_fwd": (C.c_int, [_P, _P, _I64, _P, _P, _P]),
     "alpha_penalty_bwd": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P]),
     "dng_colour_rule": (C.c_int, [_P, _P, _P, _I64, _I32, _F, _F, _I32, _I32, _F, _F, _I32, _F, _P, _P]),
+    "blender_tmp_bytes": (_SZ, [_I64]),
+    "blender_target": (C.c_int, [_P, _P, _I32, _I32, _F, _P, _P, _P, _P, _P]),
+    "dng_white_rule": (C.c_int, [_P, _P, _P, _I64, _F, _F, _P, _P]),
+    "dng_white_rule_sh": (C.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _I64, _F, _F, _P, _P, _P]),
     "l1_fwd": (C.c_int, [_P, _P, _I64, _P, _P]),
     "l1_bwd": (C.c_int, [_P, _P, _I64, _F, _P, _I32, _P]),
     "dwt_haar_fwd": (C.c_int, [_P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -312,6 +316,8 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # (tests/dtu_reference.py)
                "dtu_mask", "masked_tmp_bytes", "masked_fill_fwd", "masked_fill_bwd", "alpha_penalty_fwd", "alpha_penalty_bwd",
                "dng_colour_rule",
+               # what DNGaussian's Blender loops add (background target, white rules): restated in torch (tests/blender_reference.py)
+               "blender_tmp_bytes", "blender_target", "dng_white_rule", "dng_white_rule_sh",
                # densify / split / prune on the device: GaussianModelLite.densify_and_prune's host path is the arbiter
                # (tests/densify_reference.py restates the plan in torch)
                "densify_tmp_bytes", "densify_plan", "densify_emit", "morton_codes", "densify_gather",

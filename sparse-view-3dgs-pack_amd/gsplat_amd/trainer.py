@@ -2802,6 +2802,7 @@ class TrainerDNG(Trainer):
       the regulariser: Adam cannot sit in that tail)."""
 
     after_backward = None   # parity instrument: callable(leg "hard" | "soft" | "photometric", trainer) behind an un-fused backward
+    with_neural = True      # False (a subclass without a neural renderer): none is built, `neural` and its optimizer are None
 
     def __init__(self, model, cameras, gt_images, depth_mono, neural=None, near_centers=None, near_range=0.0, bg=None,
                  Rasterizer=None, Settings=None, criterion=None, depth_loss=None, regulariser=None, view_dirs=None, near_mask=None,
@@ -2841,16 +2842,18 @@ class TrainerDNG(Trainer):
         super().__init__(model, cameras, gt_images, criterion, Rasterizer, Settings, bg, **kw)
         if len(depth_mono) != len(cameras):
             raise ValueError("TrainerDNG: one mono depth map per training camera")
-        self.mono = [(255.0 - torch.as_tensor(d, dtype=torch.float32).to(dev)).reshape(1, 1, *d.shape[-2:]) for d in depth_mono]
-        if neural is None:
+        self.mono = self._mono_targets(depth_mono, dev)
+        if neural is None and self.with_neural:
             from dng_neural import GridRenderer
             with torch.no_grad():
                 xyz = model.params["xyz"].detach()
                 neural = GridRenderer(bound=float((xyz.max(0).values - xyz.min(0).values).max()) / 2 * 1.2,
                                       coord_center=xyz.mean(0).cpu()).to(dev)
         self.neural = neural
-        groups = neural.get_params(neural_lrs[0], neural_lrs[1])
-        if dev.type == "cuda":
+        groups = neural.get_params(neural_lrs[0], neural_lrs[1]) if neural is not None else None
+        if groups is None:
+            self.neural_optimizer = None
+        elif dev.type == "cuda":
             from .optim import FusedAdam
             self.neural_optimizer = FusedAdam(groups, lr=0.0, eps=1e-15, fuse_groups=True)
         else:
@@ -2859,6 +2862,10 @@ class TrainerDNG(Trainer):
         self.near_range = float(near_range)
         self._depth_loss, self._regulariser, self._view_dirs, self._near_mask = depth_loss, regulariser, view_dirs, near_mask
         model.optimizer.lr["opacity"] = opacity_lr   # DNGaussian/arguments/__init__.py:85 (the model's default is LGDWT-GS's)
+
+    def _mono_targets(self, depth_mono, dev):
+        """the depth legs' targets, one [1,1,H,W] per camera, formed once: 255 - depth_mono"""
+        return [(255.0 - torch.as_tensor(d, dtype=torch.float32).to(dev)).reshape(1, 1, *d.shape[-2:]) for d in depth_mono]
 
     @property
     def depth_limit(self):
@@ -2876,6 +2883,8 @@ class TrainerDNG(Trainer):
         return False
 
     def neural_parameters(self):
+        if self.neural_optimizer is None:
+            return []
         return [p for g in self.neural_optimizer.param_groups for p in g["params"]]
 
     def fused_legs_available(self):
@@ -3031,8 +3040,9 @@ class TrainerDNG(Trainer):
             g["lr"] = opt.neural_grid if g["name"] == "neural_encoder" else opt.neural_net
         return xyz_lr
 
-    def _photometric_leg(self, ci, opt):
-        """render_dng, L1 + lambda_dssim (1 - SSIM) + the per-Gaussian regulariser, backward -> (pkg, loss)"""
+    def _photometric_leg(self, ci, opt, reg_scale=None):
+        """render_dng, L1 + lambda_dssim (1 - SSIM) + the per-Gaussian regulariser (times reg_scale, a torch multiply on the 0-d
+        term, when one is given), backward -> (pkg, loss)"""
         m = self.model
         m.zero_grad()
         for p in self.neural_parameters():
@@ -3043,7 +3053,10 @@ class TrainerDNG(Trainer):
         regulariser = self._regulariser
         if regulariser is None:
             from .dng_reg import gaussian_regulariser as regulariser
-        loss = base + regulariser(act[0], pkg["opacity"], opt.shape_pena, opt.scale_pena, opt.opa_pena)
+        reg = regulariser(act[0], pkg["opacity"], opt.shape_pena, opt.scale_pena, opt.opa_pena)
+        if reg_scale is not None:
+            reg = reg * reg_scale
+        loss = base + reg
         loss.backward()
         if self.after_backward is not None:
             self.after_backward("photometric", self)
@@ -3056,6 +3069,9 @@ class TrainerDNG(Trainer):
 
     def _before_densify(self, iteration, opt, pkg):
         """behind the statistics of a densifying iteration, in front of densify_and_prune_dng (under no_grad)"""
+
+    def _after_densify(self, iteration, opt):
+        """behind densify_and_prune_dng, still under no_grad (a further prune here is part of the same re-layout)"""
 
     def _after_photometric(self, iteration, opt, pkg, stepping, stepped):
         """clean / statistics + densification / near-camera prune under no_grad, then the photometric optimizer step - without the
@@ -3077,6 +3093,7 @@ class TrainerDNG(Trainer):
                     densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
                                                         opt.split_opacity_thresh, None, generator=gen,
                                                         on_device=bool(opt.densify_on_device))
+                    self._after_densify(iteration, opt)
                     relayout = True
             if self._near_prune_due(iteration, opt):
                 # (prune_points runs in the reference even when the mask is empty - the default --near 0 makes it so - and
@@ -3305,6 +3322,331 @@ class TrainerDNGDTU(TrainerDNG):
     def restore(self, state):
         super().restore(state)
         self.ema_loss_hard = float(state.get("ema_loss_hard", 0.0))
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# DNGaussian on NeRF-synthetic: DNGaussian/train_blender.py:41-235 (`training`) and :240-395 (`training_sh`)
+# ----------------------------------------------------------------------------------------------------------------
+class DngBlenderOptions(DngOptions):
+    """DngOptions with what train_blender.py hard-codes: the patch range, depth legs every tenth iteration and only before
+    densify_until_iter, no smoothness term, no near-camera prune, the white-background mask's threshold, the white rule
+    (threshold, opacity factor) or None, the regulariser's decay after densify_until_iter, the height prune (a threshold on the
+    last coordinate, or None), and for the SH loop (`use_sh`) the plain 3DGS densification's prune opacity and size threshold
+    and the opacity reset at densify_from_iter."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.patch_range = (5, 17)                  # train_blender.py:64, :263
+        self.smooth_start = None                    # no smoothness term at any iteration
+        self.near_prune_interval = None             # no spiral cameras, no near-camera prune
+        self.near_prune_start = None
+        self.white_background = True                # run_blender.sh: every scene
+        self.depth_leg_interval = 10                # :90, :116, :289: iteration % 10 == 0, and iteration < densify_until_iter
+        self.bg_threshold = 254 / 255               # :87, :286
+        self.white_rule = (253 / 255, 0.1)          # :208-211, :367-370
+        self.reg_decay = 0.1                        # :168-169: iteration > densify_until_iter
+        self.height_prune = None                    # :215-218, :372-375: ship -0.5, hotdog -0.2
+        self.use_sh = False                         # --use_SH: training_sh (TrainerDNGBlenderSH)
+        self.prune_opacity = 0.005                  # :363 (SH loop; the neural loop takes --prune_threshold = min_opacity)
+        self.size_threshold = 20                    # :362 (SH loop), after opacity_reset_interval
+        self.reset_at_densify_from = True           # :378 (SH loop): dataset.white_background and iteration == densify_from_iter
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise TypeError("unknown option %s" % k)
+            setattr(self, k, v)
+
+    SETTINGS = {   # scripts/run_blender.sh, its three settings as plain options
+        1: dict(use_sh=False, iterations=6000, lambda_dssim=0.2, densify_grad_threshold=0.0005, min_opacity=0.01,
+                densify_until_iter=6000, densify_from_iter=500, position_lr_final=0.0000016, position_lr_max_steps=1000,
+                position_lr_start=5000, hard_depth_start=0, soft_depth_start=9999999, split_opacity_thresh=0.1,
+                error_tolerance=0.001, shape_pena=0.0, opa_pena=0.0, scale_pena=0.0, clean_iterations=[1000, 2000, 3000, 4500, 6000, 1]),
+        2: dict(use_sh=True, iterations=6000, lambda_dssim=0.2, densify_grad_threshold=0.0005, min_opacity=0.005,
+                densify_until_iter=6000, densify_from_iter=500, position_lr_final=0.0000016, position_lr_max_steps=1000,
+                position_lr_start=5000, hard_depth_start=0, error_tolerance=0.01, shape_pena=0.0, opa_pena=0.0, scale_pena=0.0,
+                clean_iterations=[1000, 2000, 3000, 4500, 6000, 1]),
+        3: dict(use_sh=True, iterations=30000, lambda_dssim=0.2, densify_grad_threshold=0.0002, min_opacity=0.005,
+                densify_until_iter=15000, densify_from_iter=500, position_lr_final=0.0000016, position_lr_max_steps=30000,
+                position_lr_start=0, hard_depth_start=99999, error_tolerance=0.2, shape_pena=0.0, opa_pena=0.0, scale_pena=0.0,
+                clean_iterations=[1000, 2000, 3000, 4500, 6000, 1]),
+    }
+    SCENES = dict(drums=1, materials=1, ship=2, lego=2, ficus=2, hotdog=2, chair=3, mic=3)
+
+    @classmethod
+    def for_scene(cls, name, **kw):
+        """scripts/run_blender.sh for one of the eight NeRF-synthetic scenes (the script tests `$dataset =~ name`, so a path
+        that contains the name will do): which loop, thresholds, learning-rate schedule, depth-leg starts, tolerance,
+        penalties, iterations - and train_blender.py's own scene tests: ship and hotdog prune below a height, chair skips the
+        white rule in the SH loop.  (--scaling_lr 0.005 and --position_lr_init 0.00016 are the model's own rates;
+        --percent_dense 0.01 its own constant.)"""
+        name = str(name)
+        hits = [k for k in cls.SCENES if k in name]
+        if not hits:
+            raise ValueError("for_scene: %r names none of %s" % (name, ", ".join(sorted(cls.SCENES))))
+        o = dict(cls.SETTINGS[cls.SCENES[hits[0]]])
+        if "ship" in name:
+            o.update(height_prune=-0.5)
+        if "hotdog" in name:
+            o.update(height_prune=-0.2)        # (a path naming both: the script prunes twice, the higher threshold decides)
+        if "chair" in name and o["use_sh"]:
+            o.update(white_rule=None)
+        o.update(kw)
+        return cls(**o)
+
+
+def _legs_due(iteration, opt):
+    return iteration < opt.densify_until_iter and iteration % opt.depth_leg_interval == 0
+
+
+def _blender_targets(trainer, depth_mono, opt, background_mask):
+    """per camera, once: the white-background mask of the ground truth and the depth legs' target 255 - mono, zero under it
+    (they depend on the inputs alone; the reference forms them again in every leg) -> (masks, targets [1,1,H,W])"""
+    dev = trainer.model.flat.device
+    masks, targets = [], []
+    with torch.no_grad():
+        for gt, d in zip(trainer.gts, depth_mono):
+            stored = torch.as_tensor(d, dtype=torch.float32).to(dev).contiguous()
+            mask, target = background_mask(torch.as_tensor(gt, dtype=torch.float32).to(dev).contiguous(), opt.bg_threshold,
+                                           mono=stored)
+            masks.append(mask)
+            targets.append(target.reshape(1, 1, *stored.shape[-2:]))
+    return masks, targets
+
+
+def _height_prune(trainer, opt):
+    """train_blender.py:215-218: prune_points(get_xyz[:, -1] < h) - the mask is one torch comparison, no stall"""
+    if opt.height_prune is None:
+        return None
+    m = trainer.model
+    return m.prune_points(m.params["xyz"].detach()[:, -1] < opt.height_prune, on_device=bool(opt.densify_on_device))
+
+
+class TrainerDNGBlender(TrainerDNG):
+    """The neural loop of DNGaussian/train_blender.py:66-228 (`training`) in its order - TrainerDNG's with what the Blender
+    script changes for a white background:
+
+      target     per camera, once (:87, :96-97): the background mask gt.min(0) > bg_threshold and the mono target
+                 255 - depth_mono with the masked pixels zero.  The depth IMAGE is not masked;
+      hard / soft legs   only on iterations divisible by depth_leg_interval and below densify_until_iter (inside their start
+                 bounds); no smoothness term; a leg's patch sizes are drawn only when it runs, hard before soft;
+      photometric  TrainerDNG's, the regulariser times reg_decay once iteration > densify_until_iter (a torch multiply on the
+                 0-d term, as the reference writes it);
+      white rule in front of every densification (:207-211), on the per-Gaussian colour of THIS iteration's photometric
+                 render (nothing has stepped since: the reference's second render gives the same tensor): statistic zeroed,
+                 raw opacity to inverse_sigmoid(factor sigmoid(opacity)); then densify_and_prune_dng; then the height prune.
+    No near-camera prune.  The last iteration steps nothing.  `clean_views` resolves to the script's SECOND definition (through
+    render_sh) in both loops; only `radii > 0` is read from it, which no colour reaches: prune_unseen through render_dng is
+    the same mask.
+
+    background_mask / white_rule: the new pieces as callables for models that are not on the GPU (defaults:
+      gsplat_amd.dng_blender's).  opt: the DngBlenderOptions whose bg_threshold forms the masks (default: its defaults).
+      bg defaults to white.
+    train_iteration's dict gains rule_count (the device count of a densifying iteration, else None) and height_pruned.
+    Everything closed to TrainerDNG is closed here."""
+
+    def __init__(self, model, cameras, gt_images, depth_mono, opt=None, background_mask=None, white_rule=None, bg=None, **kw):
+        if bg is None:
+            bg = torch.ones(3, dtype=torch.float32, device=model.flat.device)
+        if background_mask is None or white_rule is None:
+            from . import dng_blender
+            background_mask = background_mask or dng_blender.blender_background_mask
+            white_rule = white_rule or dng_blender.white_rule
+        self._white_rule, self._background_mask = white_rule, background_mask
+        self._target_options = DngBlenderOptions() if opt is None else opt
+        super().__init__(model, cameras, gt_images, depth_mono, bg=bg, **kw)
+        self._rule_count = self._height_pruned = None
+
+    def _mono_targets(self, depth_mono, dev):
+        self.bg_masks, targets = _blender_targets(self, depth_mono, self._target_options, self._background_mask)
+        return targets
+
+    def _near_prune_due(self, iteration, opt):
+        return False
+
+    def _before_densify(self, iteration, opt, pkg):
+        self._rule_count = None
+        if opt.white_rule is None:
+            return
+        m = self.model
+        thr, factor = opt.white_rule
+        self._rule_count = self._white_rule(pkg["color"].detach(), m.xyz_gradient_accum, m.params["opacity"].detach(), thr, factor)
+
+    def _after_densify(self, iteration, opt):
+        self._height_pruned = _height_prune(self, opt)
+
+    def train_iteration(self, iteration, opt):
+        """One iteration (1-based) of train_blender.py:66-228 in its order.  Returns TrainerDNG's dict (near_pruned: always
+        None) plus rule_count and height_pruned."""
+        self.last_options = opt
+        m = self.model
+        xyz_lr = self._set_rates(iteration, opt)
+        ci = self.draw_cameras(opt.seed)
+        stepping = iteration < opt.iterations
+        lo, hi = opt.patch_range
+        patches = [None, None, None, None]
+        losses, path = dict(hard=None, soft=None), dict(hard=None, soft=None)
+        stepped = dict(hard=False, soft=False, gaussians=False, neural=False)
+        due = _legs_due(iteration, opt)
+        for k, (name, kind, start) in enumerate((("hard", "means", opt.hard_depth_start), ("soft", "opacity", opt.soft_depth_start))):
+            if due and iteration > start:
+                patches[2 * k] = self._rng.randint(lo, hi)
+                patches[2 * k + 1] = self._rng.randint(lo, hi)
+                losses[name], path[name] = self._depth_leg(ci, kind, patches[2 * k], patches[2 * k + 1], 0.0, opt, stepping)
+                stepped[name] = stepping
+        self._rule_count = self._height_pruned = None
+        pkg, loss = self._photometric_leg(ci, opt, reg_scale=opt.reg_decay if iteration > opt.densify_until_iter else None)
+        cleaned, densified, _ = self._after_photometric(iteration, opt, pkg, stepping, stepped)
+        return dict(loss=loss.detach(), loss_hard=losses["hard"], loss_soft=losses["soft"], camera=ci, patches=tuple(patches),
+                    xyz_lr=xyz_lr, stepped=stepped, densified=densified, near_pruned=None, cleaned=cleaned, P=m.P, path=path,
+                    rule_count=self._rule_count, height_pruned=self._height_pruned)
+
+
+def render_dng_sh(viewpoint_camera, pc, Rasterizer, Settings, bg_color, scaling_modifier=1.0, debug=False):
+    """= render_sh() of DNGaussian/gaussian_renderer/__init__.py:285-367: the FSGS-generation rasterizer with the model's SH rows
+    -> {render, depth, alpha, viewspace_points, visibility_filter, radii, opacity}; the image is NOT clamped.  The reference's
+    "color" key (the per-Gaussian colour, evaluated in Python on every call and read only by the white rule) is not formed
+    here: dng_blender.white_rule_sh evaluates it inside its kernel when the rule runs and hands it back."""
+    xyz = pc.get_xyz
+    screenspace_points = torch.zeros_like(xyz, dtype=xyz.dtype, requires_grad=True) + 0
+    try:
+        screenspace_points.retain_grad()
+    except Exception:
+        pass
+    opacity = pc.get_opacity
+    rs = _settings_of(Settings, viewpoint_camera, bg_color, pc.active_sh_degree, xyz.shape[0], scaling_modifier, debug)
+    image, radii, depth, alpha = Rasterizer(raster_settings=rs)(
+        means3D=xyz, means2D=screenspace_points, shs=pc.get_features, colors_precomp=None, opacities=opacity,
+        scales=pc.get_scaling, rotations=pc.get_rotation, cov3D_precomp=None)
+    return {"render": image, "depth": depth, "alpha": alpha, "viewspace_points": screenspace_points,
+            "visibility_filter": radii > 0, "radii": radii, "opacity": opacity}
+
+
+class TrainerDNGBlenderSH(TrainerDNG):
+    with_neural = False
+
+    """The SH loop of DNGaussian/train_blender.py:265-388 (`training_sh`) in its order, one GPU: a plain SH model, no neural
+    renderer, no soft leg, no regulariser.
+
+      SH ramp    oneupSHdegree every sh_increase_interval (1000) iterations;
+      hard leg   as TrainerDNGBlender's (the depth-only pass at opacity 0.95, the zeroed target, Adam on `xyz` ONLY);
+      photometric  render_dng_sh, L1 + lambda_dssim (1 - SSIM), backward, then - un-fused - Adam on every group;
+      densification  the plain 3DGS rule, densify_and_prune(max_grad, prune_opacity, extent, size_threshold after
+                 opacity_reset_interval);  AFTER it the white rule through white_rule_sh on the re-laid-out model with this
+                 camera's centre (the statistic it zeroes has just been zeroed by the re-layout; the opacity edit is what a
+                 user's model shows), then the height prune;
+      reset_opacity()  every opacity_reset_interval and, for a white background, at densify_from_iter - there WITHOUT a
+                 densification: only the opacity group's step is cancelled and its moments zeroed.
+    A re-layout cancels the step of every group, as in the siblings.  The last iteration steps nothing.
+    start_checkpoint: `training_sh` calls gaussians.load_shape, which no class of the reference defines - starting the SH loop
+      from a (neural) checkpoint cannot work there and is refused here.
+    background_mask / white_rule_sh / depth_loss: callables for models that are not on the GPU (defaults:
+      gsplat_amd.dng_blender's and depth_norm.depth_regulariser).  Everything closed to TrainerDNG is closed here."""
+
+    def __init__(self, model, cameras, gt_images, depth_mono, opt=None, bg=None, Rasterizer=None, Settings=None, criterion=None,
+                 depth_loss=None, background_mask=None, white_rule_sh=None, opacity_lr=0.05, lambda_dssim=0.2, depth_limit=None,
+                 fused_step=False, side_launch=False, start_checkpoint=None, **kw):
+        if start_checkpoint is not None:
+            raise RuntimeError("TrainerDNGBlenderSH: train_blender.py's training_sh restores a checkpoint through "
+                               "gaussians.load_shape, which no class of the reference defines; starting the SH loop from a "
+                               "neural checkpoint is refused")
+        if background_mask is None or white_rule_sh is None:
+            from . import dng_blender
+            background_mask = background_mask or dng_blender.blender_background_mask
+            white_rule_sh = white_rule_sh or dng_blender.white_rule_sh
+        self._white_rule_sh, self._background_mask = white_rule_sh, background_mask
+        self._target_options = DngBlenderOptions(use_sh=True) if opt is None else opt
+        if bg is None:
+            bg = torch.ones(3, dtype=torch.float32, device=model.flat.device)
+        super().__init__(model, cameras, gt_images, depth_mono, bg=bg, Rasterizer=Rasterizer, Settings=Settings, criterion=criterion,
+                         depth_loss=depth_loss, opacity_lr=opacity_lr, lambda_dssim=lambda_dssim, depth_limit=depth_limit,
+                         fused_step=fused_step, side_launch=side_launch, **kw)
+        self.last_colour = None   # the per-Gaussian colour of the last white rule (render_sh's "color"), or None
+
+    _mono_targets = TrainerDNGBlender._mono_targets
+
+    def _render(self, cam, activations=None):
+        return render_dng_sh(cam, self.model, self.Rasterizer, self.Settings, self.bg)
+
+    def train_iteration(self, iteration, opt):
+        """One iteration (1-based) of train_blender.py:265-388 in its order.  Returns dict(loss, loss_hard, camera, patches
+        (hard local, hard global; None when the leg did not run), xyz_lr, sh_degree, stepped = dict(hard, gaussians, opacity),
+        densified (3DGS's 3-tuple or None), rule_count (device count or None), height_pruned, cleaned, reset, P, path)."""
+        self.last_options = opt
+        m, o = self.model, self.model.optimizer
+        xyz_lr = m.update_learning_rate(max(iteration - opt.position_lr_start, 0), opt.position_lr_final, opt.position_lr_delay_mult,
+                                        opt.position_lr_max_steps)
+        o.lr["opacity"] = opt.opacity_lr
+        if iteration % opt.sh_increase_interval == 0:
+            m.oneupSHdegree()
+        ci = self.draw_cameras(opt.seed)
+        cam = self.cameras[ci]
+        stepping = iteration < opt.iterations
+        lo, hi = opt.patch_range
+        patches, loss_hard, path = [None, None], None, None
+        stepped = dict(hard=False, gaussians=False, opacity=False)
+        if iteration > opt.hard_depth_start and _legs_due(iteration, opt):
+            patches = [self._rng.randint(lo, hi), self._rng.randint(lo, hi)]
+            loss_hard, path = self._depth_leg(ci, "means", patches[0], patches[1], 0.0, opt, stepping)
+            stepped["hard"] = stepping
+        m.zero_grad()
+        pkg = self._render(cam)
+        loss, l1, ssim_value = self.criterion.photometric(pkg["render"], self.gts[ci], l1_weight=1.0)
+        loss.backward()
+        if self.after_backward is not None:
+            self.after_backward("photometric", self)
+        self.last = dict(loss=loss.detach(), radii=pkg["radii"], parts=dict(l1=l1.detach(), ssim=ssim_value.detach()), path="unfused")
+        self.last_radii = pkg["radii"]
+        cleaned = densified = rule_count = height_pruned = None
+        relayout = reset = False
+        with torch.no_grad():
+            m.collect_grads()
+            clean = iteration in opt.clean_iterations
+            if clean:
+                cleaned = self.prune_unseen(opt=opt)
+                relayout = True
+            if iteration < opt.densify_until_iter and not clean:
+                m.update_view_statistics(pkg["radii"], pkg["viewspace_points"].grad)
+                if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+                    thr = opt.size_threshold if iteration > opt.opacity_reset_interval else None
+                    gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
+                    densified = m.densify_and_prune(opt.densify_grad_threshold, opt.prune_opacity, opt.cameras_extent, thr,
+                                                    generator=gen, on_device=bool(opt.densify_on_device))
+                    if opt.white_rule is not None:
+                        rule_thr, factor = opt.white_rule
+                        rule_count, self.last_colour = self._white_rule_sh(
+                            m.params["xyz"].detach(), m.params["features"].detach(), m.active_sh_degree, cam.camera_center,
+                            m.xyz_gradient_accum, m.params["opacity"].detach(), rule_thr, factor, return_colour=True)
+                    height_pruned = _height_prune(self, opt)
+                    relayout = True
+                if iteration % opt.opacity_reset_interval == 0 or (
+                        opt.white_background and opt.reset_at_densify_from and iteration == opt.densify_from_iter):
+                    m.reset_opacity()
+                    reset = True
+            if stepping and not relayout:
+                o.step(skip=("opacity",) if reset else ())
+                stepped["gaussians"], stepped["opacity"] = True, not reset
+            m.zero_grad()
+        return dict(loss=loss.detach(), loss_hard=loss_hard, camera=ci, patches=tuple(patches), xyz_lr=xyz_lr,
+                    sh_degree=m.active_sh_degree, stepped=stepped, densified=densified, rule_count=rule_count,
+                    height_pruned=height_pruned, cleaned=cleaned, reset=reset, P=m.P, path=path)
+
+    def checkpoint(self):
+        """Trainer.checkpoint() plus the loop's RNG and camera stack"""
+        state = Trainer.checkpoint(self)
+        state["rng"] = None if self._rng is None else self._rng.getstate()
+        state["stack"] = list(self._stack)
+        return state
+
+    def restore(self, state):
+        """the inverse of checkpoint() - of THIS loop's checkpoints; one that carries a neural renderer is the other loop's"""
+        import random
+        if "neural" in state:
+            raise RuntimeError("TrainerDNGBlenderSH: a neural checkpoint (the reference would go through load_shape, which no class "
+                               "defines) is refused")
+        self.model.restore(state)
+        if state.get("rng") is not None:
+            self._rng = random.Random()
+            self._rng.setstate(state["rng"])
+        self._stack = list(state["stack"])
 
 
 # ----------------------------------------------------------------------------------------------------------------
