@@ -1266,6 +1266,37 @@ int gs_eval_metrics(const float* render, const float* gt, const float* mask /*NU
                     int32_t H, int32_t W, int32_t flags, float C1, float C2, void* tmp, size_t tmp_bytes,
                     double* out_row /*[GS_EVAL_WORDS], device*/, uint8_t* quantised_out /*NULL ok*/, void* stream);
 
+/* ---- evaluation from files (csrc/gs_eval_files.hip): PIL.Image.resize on 8-bit images, and skimage's SSIM ----
+ * gs_resize_bicubic_u8: in uint8 [H,W,C] interleaved, C = 1 or 3 -> out uint8 [H2,W2,C], the bytes Pillow's
+ * Image.resize((W2, H2)) gives for modes L and RGB with its default filter (antialiased bicubic, Resample.c), and, when
+ * out_f32 is given, the same image as fp32 planar [C,H2,W2] = byte / 255 (to_tensor; what gs_eval_metrics takes).
+ * The per-axis tables are the caller's, in device memory (gsplat_amd/imageio.py forms them in double on the host):
+ *   bounds int32 [n_out,2] = (first source sample, run length n <= ksize) per output sample;
+ *   coef   int32 [n_out,ksize] = the normalised weights * 2^22, rounded half away from zero, zero beyond the run.
+ * out = clamp((2^21 + sum coef * sample) >> 22, 0, 255) in int32, the horizontal pass first into an 8-bit intermediate
+ * (tmp), then the vertical pass.  A pass whose sizes agree is skipped (its tables may be NULL); with both skipped the image
+ * is copied.  A table row whose run leaves the source reads nothing and gives 0.  At most two launches on `stream`.
+ * tmp: >= gs_resize_tmp_bytes(H, W, C, H2, W2) bytes of device scratch = the intermediate when both passes run, else 0
+ * (tmp may then be NULL).  GS_E_NULL: in, out, a needed table or needed tmp missing; GS_E_SHAPE: C outside {1, 3}, a size
+ * <= 0, an image above 2^30 bytes, ksize <= 0 for a pass that runs, or tmp_bytes too small.
+ *
+ * gs_eval_ssim_sk: out[0] (one double, device memory) = skimage.metrics.structural_similarity(a, b, channel_axis=2,
+ * data_range=1.0) with its defaults, of render and gt [C,H,W] fp32 after gs_eval_metrics's pixel transform (same flags, same
+ * order, the one implementation): per channel the 7 x 7 box means ux, uy, uxx, uyy, uxy, v_ab = 49/48 (u_ab - u_a u_b),
+ * S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = 1e-4, C2 = 9e-4, the mean of S over the windows
+ * that lie wholly inside the image (skimage's 3-pixel crop), then the mean over the channels.  Window sums and the map sum
+ * are float64 in one fixed order: the same bits on every run.  Two launches, no atomics, no host synchronisation.
+ * tmp: >= gs_eval_ssim_sk_tmp_bytes(C, H, W).  GS_E_NULL: render, gt, tmp or out missing, or GS_EVAL_MASK_DTU without mask;
+ * GS_E_SHAPE: C outside 1..4, H < 7 or W < 7 (skimage raises there), unknown flag bits, or tmp_bytes too small. */
+size_t gs_resize_tmp_bytes(int32_t H, int32_t W, int32_t C, int32_t H2, int32_t W2);
+int gs_resize_bicubic_u8(const uint8_t* in, int32_t H, int32_t W, int32_t C, int32_t H2, int32_t W2,
+                         const int32_t* xbounds, const int32_t* xcoef, int32_t kx, const int32_t* ybounds,
+                         const int32_t* ycoef, int32_t ky, void* tmp, size_t tmp_bytes, uint8_t* out,
+                         float* out_f32 /*NULL ok*/, void* stream);
+size_t gs_eval_ssim_sk_tmp_bytes(int32_t C, int32_t H, int32_t W);
+int gs_eval_ssim_sk(const float* render, const float* gt, const float* mask /*NULL unless GS_EVAL_MASK_DTU*/, int32_t C,
+                    int32_t H, int32_t W, int32_t flags, void* tmp, size_t tmp_bytes, double* out /*device*/, void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

@@ -11,6 +11,7 @@
 // masked sum (a-b)^2 and its element count (float64).  One row of partials per workgroup, plain stores, no atomics.
 // eval_finish_kernel: one workgroup adds the rows in index order in float64 and writes the view's GS_EVAL_WORDS doubles.
 #include "gs_common.h"
+#include "gs_eval_px.h"
 
 namespace {
 
@@ -44,18 +45,7 @@ inline int64_t ev_tiles(int C, int H, int W) {
   return (int64_t)((W + EV_ST - 1) / EV_ST) * ((H + EV_ST - 1) / EV_ST) * C;
 }
 
-// torchvision save_image's byte: mul(255).add_(0.5).clamp_(0, 255).to(uint8) - two separately rounded fp32 operations
-__device__ __forceinline__ uint8_t ev_byte(float x) {
-  const float s = __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
-  return (uint8_t)(int)fminf(fmaxf(s, 0.f), 255.f);
-}
-// the pixel as the metrics see it; m is read only with GS_EVAL_MASK_DTU
-__device__ __forceinline__ float ev_transform(float x, float m, int flags) {
-  if (flags & GS_EVAL_CLAMP) x = fminf(fmaxf(x, 0.f), 1.f);
-  if (flags & GS_EVAL_QUANTISE) x = __fdiv_rn((float)ev_byte(x), 255.0f);  // to_tensor
-  if (flags & GS_EVAL_MASK_DTU) x = __fadd_rn(__fmul_rn(x, m), __fsub_rn(1.0f, m));
-  return x;
-}
+// (ev_byte and ev_transform, the pixel as the metrics see it: gs_eval_px.h, shared with gs_eval_files.hip)
 
 // Halo tile of both images, transformed, into tile[0] (render) and tile[1] (gt).  Outside the image the tile holds 0: the
 // convolution pads with zero AFTER the blend, as F.conv2d does.  With W a multiple of 4 and 16-byte aligned planes the

@@ -290,6 +290,10 @@ PROTOTYPES = {
     "eval_partials_count": (C.c_int64, [_I32, _I32, _I32]),
     "eval_tmp_bytes": (_SZ, [_I32, _I32, _I32]),
     "eval_metrics": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _F, _F, _P, _SZ, _P, _P, _P]),
+    "resize_tmp_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32]),
+    "resize_bicubic_u8": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _SZ, _P, _P, _P]),
+    "eval_ssim_sk_tmp_bytes": (_SZ, [_I32, _I32, _I32]),
+    "eval_ssim_sk": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -330,6 +334,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                "densify_plan_gated", "prune_tmp_bytes", "prune_plan", "prune_emit",
                # test-set evaluation (PSNR / SSIM / L1 per view): restated in torch (tests/eval_reference.py)
                "eval_partials_count", "eval_tmp_bytes", "eval_metrics",
+               # evaluation from files: Pillow's resize restated in numpy (gsplat_amd/imageio.py, pinned by tests/golden/pil_resize.npz)
+               # and skimage's SSIM in float64 numpy (tests/eval_files_reference.py)
+               "resize_tmp_bytes", "resize_bicubic_u8", "eval_ssim_sk_tmp_bytes", "eval_ssim_sk",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",

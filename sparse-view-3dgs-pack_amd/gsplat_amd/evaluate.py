@@ -8,8 +8,17 @@ from one pass over the two images, in the forms the reference's evaluation compu
 The pixel transform runs in this order on both images: clamp to [0, 1], the 8-bit round trip of torchvision's save_image /
 to_tensor, the blend to white under the mask.  Divergences from the reference, all raised or documented: one view per call
 (the reference-named psnr / ssim loop over a batch), fp32 CUDA(HIP) tensors only, at most 4 channels, the DTU mask is ONE
-[H,W] plane broadcast over the channels (the reference's is a 3-channel image; DTU's masks are grey), images arrive at the
-mask's size (no Image.resize), no LPIPS, no SSIM_sk, no PNG encoding (the bytes are offered).
+[H,W] plane broadcast over the channels (the reference's is a 3-channel image; DTU's masks are grey), no LPIPS (its weights
+cannot be obtained; the renders/ and gt/ folders are the hand-off, gsplat_amd/render_set.py).  The three other gaps this
+list used to name are closed beside this file: Image.resize and the PNG files in gsplat_amd/imageio.py, the evaluation from
+those files in gsplat_amd/render_set.py (evaluate_dir resizes to the mask's size as metrics_dtu.py:37-39 does; the functions
+HERE still take images that already have the mask's size), and SSIM_sk here, on request:
+
+  ssim_sk=True    skimage.metrics.structural_similarity(channel_axis=2, data_range=1.0) of the transformed pair
+                  (DNGaussian/metrics.py:81, metrics_dtu.py:94), csrc/gs_eval_files.hip: word 5 of a view's row, "ssim_sk" of
+                  image_metrics, "SSIM_sk" (the mean only, metrics.py:93-99) of Evaluator.result().  float64 throughout, where
+                  skimage runs float32 on the reference's arrays: 2e-10 to 8e-7 apart on the tests' cases.  skimage is not a dependency and the
+                  definition is taken from its documented algorithm.  Images below 7 x 7 raise.
 
 Nothing here synchronises with the host: a view's numbers are float64 words in device memory, and Evaluator.result() is the
 one read-back of a whole test set."""
@@ -23,7 +32,8 @@ from .io import write_results_json  # noqa: F401  (the evaluation's files: resul
 CLAMP, QUANTISE, MASK_DTU = 1, 2, 4  # GS_EVAL_CLAMP, GS_EVAL_QUANTISE, GS_EVAL_MASK_DTU
 WORDS = 8                            # GS_EVAL_WORDS: mse, psnr, ssim, l1, count, 3 reserved
 C1, C2 = 0.01 ** 2, 0.03 ** 2        # utils/loss_utils.py (_ssim)
-_MSE, _PSNR, _SSIM, _L1, _COUNT = range(5)
+_MSE, _PSNR, _SSIM, _L1, _COUNT, _SSIM_SK = range(6)   # (word 5 is reserved = 0 unless ssim_sk is asked for)
+SK_WIN = 7                           # skimage's default win_size: smaller images raise there
 
 
 def _stream(t):
@@ -79,16 +89,37 @@ def _tmp(device, Cn, H, W):
     return torch.empty((int(hip_api().raw("eval_tmp_bytes")(Cn, H, W)),), dtype=torch.uint8, device=device)
 
 
-def image_metrics(render, gt, mask=None, clamp=False, quantise=False, return_bytes=False):
+def _sk_check(H, W):
+    if H < SK_WIN or W < SK_WIN:
+        raise ValueError("ssim_sk: images of at least %d x %d (got %d x %d) - skimage raises there too" % (SK_WIN, SK_WIN, H, W))
+
+
+def _sk_tmp(device, Cn, H, W):
+    return torch.empty((int(hip_api().raw("eval_ssim_sk_tmp_bytes")(Cn, H, W)),), dtype=torch.uint8, device=device)
+
+
+def _launch_sk(render, gt, mask, Cn, H, W, flags, tmp, out):
+    """out (one float64 word in device memory) <- SSIM_sk of the transformed pair; on the stream of _launch, after it"""
+    hip_api().call("eval_ssim_sk", render.data_ptr(), gt.data_ptr(), None if mask is None else mask.data_ptr(), Cn, H, W,
+                   int(flags), tmp.data_ptr(), tmp.numel(), out.data_ptr(), _stream(render))
+
+
+def image_metrics(render, gt, mask=None, clamp=False, quantise=False, return_bytes=False, ssim_sk=False):
     """-> {"mse", "psnr", "ssim", "l1", "count"}: 0-d float64 device tensors (views of one row), plus "bytes" - the uint8
-    [H,W,C] image torchvision's save_image would write for `render` - when return_bytes.  Identical images give
-    psnr = +inf; an empty mask gives mse = psnr = NaN, as in the reference."""
+    [H,W,C] image torchvision's save_image would write for `render` - when return_bytes, plus "ssim_sk" (skimage's
+    structural_similarity of the same transformed pair) when ssim_sk.  Identical images give psnr = +inf; an empty mask
+    gives mse = psnr = NaN, as in the reference."""
     render, gt, mask, Cn, H, W = _check(render, gt, mask)
+    if ssim_sk:
+        _sk_check(H, W)
     dev = render.device
     row = torch.empty((WORDS,), dtype=torch.float64, device=dev)
     q = torch.empty((H, W, Cn), dtype=torch.uint8, device=dev) if return_bytes else None
     _launch(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), _tmp(dev, Cn, H, W), row, q)
     out = {"mse": row[_MSE], "psnr": row[_PSNR], "ssim": row[_SSIM], "l1": row[_L1], "count": row[_COUNT]}
+    if ssim_sk:
+        _launch_sk(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), _sk_tmp(dev, Cn, H, W), row[_SSIM_SK:_SSIM_SK + 1])
+        out["ssim_sk"] = row[_SSIM_SK]
     if return_bytes:
         out["bytes"] = q
     return out
@@ -120,10 +151,11 @@ def ssim(img1, img2, window_size=11, size_average=True):
 
 class Evaluator:
     """The [n_views, 8] float64 device table of a test set and the scratch of its one image size.  add() writes a row with two
-    launches and no host wait; result() is the one read-back."""
+    launches (four with ssim_sk, which fills word 5 of the row) and no host wait; result() is the one read-back."""
     FILL = float("nan")   # rows no view was added to
+    ssim_sk = False       # (a table filled by hand, as the tests do, reports what the defaults report)
 
-    def __init__(self, n_views, C, H, W, device):
+    def __init__(self, n_views, C, H, W, device, ssim_sk=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("Evaluator: CUDA(HIP) device only - there is no CPU path")
@@ -132,6 +164,10 @@ class Evaluator:
         self.shape = (int(C), int(H), int(W))
         self.table = torch.full((int(n_views), WORDS), self.FILL, dtype=torch.float64, device=device)
         self.tmp = _tmp(device, *self.shape)   # (views are added on one stream: the launches of two views never overlap)
+        self.ssim_sk = bool(ssim_sk)
+        if self.ssim_sk:
+            _sk_check(int(H), int(W))
+            self.sk_tmp = _sk_tmp(device, *self.shape)
 
     def add(self, i, render, gt, mask=None, clamp=False, quantise=False):
         """Row i <- the metrics of this view."""
@@ -142,10 +178,14 @@ class Evaluator:
             raise ValueError("Evaluator.add: view is %s on %s, the table was built for %s on %s"
                              % ((Cn, H, W), render.device, self.shape, self.table.device))
         _launch(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), self.tmp, self.table[int(i)], None)
+        if self.ssim_sk:
+            _launch_sk(render, gt, mask, Cn, H, W, _flags(mask, clamp, quantise), self.sk_tmp,
+                       self.table[int(i), _SSIM_SK:_SSIM_SK + 1])
 
     def result(self, names=None):
         """The one read-back -> {"SSIM", "PSNR", "L1", "per_view": {"SSIM": {name: v}, "PSNR": {...}, "L1": {...}}}.  The means
-        are plain means of the per-view values (metrics.py:76-83: torch.tensor(psnrs).mean())."""
+        are plain means of the per-view values (metrics.py:76-83: torch.tensor(psnrs).mean()).  An Evaluator built with
+        ssim_sk adds "SSIM_sk": the mean only, no per-view entry, as DNGaussian/metrics.py:93-99 stores it."""
         table = self.table.cpu()
         n = table.shape[0]
         names = ["%05d.png" % i for i in range(n)] if names is None else list(names)   # render.py:45 names its files so
@@ -156,6 +196,8 @@ class Evaluator:
             vals = [float(v) for v in table[:, col]]
             out[key] = sum(vals) / n
             per[key] = dict(zip(names, vals))
+        if self.ssim_sk:
+            out["SSIM_sk"] = sum(float(v) for v in table[:, _SSIM_SK]) / n
         out["per_view"] = per
         return out
 
