@@ -495,7 +495,7 @@ int gso_activations_bwd(const float* scaling, const float* rotation, const float
     const float* g = g_rot + 4 * (size_t)i;
     float* d = d_rotation + 4 * (size_t)i;
     const float norm = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    if (norm > 1e-12f) {
+    if (norm >= 1e-12f) {  // (>=: clamp_min passes the gradient at the tie)
       const float inv = 1.0f / norm;
       const float v[4] = {q[0] * inv, q[1] * inv, q[2] * inv, q[3] * inv};
       const float dot = v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3];

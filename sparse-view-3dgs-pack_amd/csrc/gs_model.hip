@@ -5,7 +5,9 @@
 //   * densification statistics  max_radii2D[vis] = max(., radii[vis]), xyz_gradient_accum[vis] += |dL_dmean2D.xy|,
 //     denom[vis] += 1  (train.py:266-268, gaussian_model.py:471-473) in one kernel.
 // Arithmetic restates what torch does for these ops (exp, F.normalize with eps 1e-12, sigmoid and their autograd
-// formulas); pinned against torch autograd in tests/test_model_ops.py.
+// formulas); held per element to a float64 restatement of those semantics at the clamp, tie, saturation and overflow edges
+// in tests/test_gpu_model_ops.py (the restatement, its bars and its cases: tests/model_ops_reference.py, proved against torch
+// autograd in tests/test_model_ops_cases_cpu.py).
 #include <math.h>
 
 #include "gs_common.h"
@@ -47,7 +49,9 @@ __global__ void __launch_bounds__(GS_BLOCK) act_bwd_kernel(const float* __restri
   const float4 g = make_float4(g_rot[4 * i], g_rot[4 * i + 1], g_rot[4 * i + 2], g_rot[4 * i + 3]);
   const float norm = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
   float4 d;
-  if (norm > 1e-12f) {
+  // (>=: torch's clamp_min passes the gradient where norm >= eps, the tie included - an axis-aligned q = (1e-12f, 0, 0, 0)
+  //  reaches it, sqrt(fl(e e)) == e)
+  if (norm >= 1e-12f) {
     const float inv = 1.0f / norm;
     const float vx = q.x * inv, vy = q.y * inv, vz = q.z * inv, vw = q.w * inv;
     const float dot = vx * g.x + vy * g.y + vz * g.z + vw * g.w;

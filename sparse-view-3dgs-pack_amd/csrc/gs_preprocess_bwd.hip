@@ -489,7 +489,7 @@ __global__ void __launch_bounds__(GS_BLOCK, 4) preprocess_bwd_step_kernel(Prepro
       const float4 q = make_float4(qr[0], qr[1], qr[2], qr[3]);
       const float norm = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
       float g[4];
-      if (norm > 1e-12f) {
+      if (norm >= 1e-12f) {  // (>=: clamp_min passes the gradient at the tie, as in act_bwd_kernel)
         const float inv = 1.0f / norm;
         const float vx = q.x * inv, vy = q.y * inv, vz = q.z * inv, vw = q.w * inv;
         const float dot = vx * gb.dq[0] + vy * gb.dq[1] + vz * gb.dq[2] + vw * gb.dq[3];

@@ -100,6 +100,22 @@ def unfused_step_with_rows(hip, a, ci):
 
 
 # ---- the step kernel -----------------------------------------------------------------------------------------------------
+def fused_equals_the_four_kernels(hip, a, b, steps=3):
+    """`a` un-fused, `b` fused on a's blend sums, `steps` consecutive steps from the same model: parameters, both moments and the
+    three statistics torch.equal after every one -> a's last state.  (tests/test_gpu_model_ops.py runs it on its own rows.)"""
+    assert torch.equal(a.model.flat, b.model.flat)
+    for it in range(steps):
+        b.rows_override = unfused_step_with_rows(hip, a, it)
+        b._step_camera(it, True, ())
+        torch.cuda.synchronize()
+        assert b.last["path"] == "fused"
+        sa, sb = state(a), state(b)
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), (it, k, float((sa[k] - sb[k]).abs().max()))
+        assert a.model.optimizer.t == b.model.optimizer.t and a.model.optimizer.seg_steps == b.model.optimizer.seg_steps
+    return sa
+
+
 @pytest.mark.parametrize("deg", [0, 3])
 @pytest.mark.parametrize("size", [(160, 128), (150, 100)], ids=["160x128", "150x100"])
 @pytest.mark.parametrize("P", [1, 3, 1023, 30000])
@@ -109,17 +125,8 @@ def test_fused_step_equals_the_four_kernels_bit_for_bit(hip, P, size, deg):
     float4 grid, images whose tiles are cut by the border, a share of the Gaussians outside every frustum."""
     W, H = size
     a, b = make(hip, False, P=P, W=W, H=H, deg=deg), make(hip, True, P=P, W=W, H=H, deg=deg)
-    assert torch.equal(a.model.flat, b.model.flat)
     start = a.model.flat.detach().clone()
-    for it in range(3):
-        b.rows_override = unfused_step_with_rows(hip, a, it)
-        b._step_camera(it, True, ())
-        torch.cuda.synchronize()
-        assert b.last["path"] == "fused"
-        sa, sb = state(a), state(b)
-        for k in sa:
-            assert torch.equal(sa[k], sb[k]), (it, k, float((sa[k] - sb[k]).abs().max()))
-        assert a.model.optimizer.t == b.model.optimizer.t and a.model.optimizer.seg_steps == b.model.optimizer.seg_steps
+    sa = fused_equals_the_four_kernels(hip, a, b)
     assert float((sa["flat"] - start).abs().max()) > 0 and float(sa["denom"].max()) >= 1.0
     if P >= 3:   # some rows are outside every frustum: never seen
         assert float(sa["denom"].min()) == 0.0

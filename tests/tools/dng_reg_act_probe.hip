@@ -60,9 +60,44 @@ static int run(const char* what, float lo, float hi, int n, bool sigmoid) {
   return 0;
 }
 
+// exp over a range that leaves fp32's normal numbers at both ends (tests/model_ops_reference.py takes its E from this line):
+// the relative error where the float64 result is a normal fp32 number, the absolute error (in units of FLT_MIN) where it is
+// below them, and the arguments at which the fp32 result and the rounded float64 result disagree about being infinite.
+static int run_exp_wide(float lo, float hi, int n) {
+  std::vector<float> r(n), s(n);
+  for (int i = 0; i < n; i++) r[i] = (float)((double)lo + ((double)hi - (double)lo) * i / (n - 1));
+  float *dr, *ds, *dout, *dom;
+  CHECK(hipMalloc(&dr, 4 * (size_t)n)); CHECK(hipMalloc(&ds, 4 * (size_t)n));
+  CHECK(hipMalloc(&dout, 4 * (size_t)n)); CHECK(hipMalloc(&dom, 4 * (size_t)n));
+  CHECK(hipMemcpy(dr, r.data(), 4 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dr, n, ds, dout, dom);
+  CHECK(hipGetLastError());
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipMemcpy(s.data(), ds, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  CHECK(hipFree(dr)); CHECK(hipFree(ds)); CHECK(hipFree(dout)); CHECK(hipFree(dom));
+  const double flt_min = std::ldexp(1.0, -126), u = std::ldexp(1.0, -24);
+  double rel = 0.0, sub = 0.0;
+  int inf_differs = 0;
+  for (int i = 0; i < n; i++) {
+    const double w = std::exp((double)r[i]), g = (double)s[i];
+    if (std::isinf((float)w) || std::isinf(s[i])) {
+      inf_differs += std::isinf((float)w) != std::isinf(s[i]);
+    } else if (w >= flt_min) {
+      rel = std::fmax(rel, std::fabs(g - w) / w);
+    } else {
+      sub = std::fmax(sub, std::fabs(g - w) / flt_min);
+    }
+  }
+  std::printf("exp over [%g, %g], %d arguments: max relative error %.4e (%.3f x 2^-24) where the result is a normal number; "
+              "below them max absolute error %.4e x 2^-126; infinite on one side only at %d arguments\n",
+              lo, hi, n, rel, rel / u, sub, inf_differs);
+  return 0;
+}
+
 int main() {
   const int n = 1 << 22;
   if (run("exp", -7.f, 1.5f, n, false)) return 1;
   if (run("sigmoid", -7.f, 7.f, n, true)) return 1;
+  if (run_exp_wide(-104.f, 89.f, n)) return 1;
   return 0;
 }
