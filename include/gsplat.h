@@ -1297,6 +1297,35 @@ size_t gs_eval_ssim_sk_tmp_bytes(int32_t C, int32_t H, int32_t W);
 int gs_eval_ssim_sk(const float* render, const float* gt, const float* mask /*NULL unless GS_EVAL_MASK_DTU*/, int32_t C,
                     int32_t H, int32_t W, int32_t flags, void* tmp, size_t tmp_bytes, double* out /*device*/, void* stream);
 
+/* ---- the turbo-coloured depth map of the render stage (csrc/gs_depth_vis.hip) ----
+ * DNGaussian/render.py:121,127-130 (and spiral.py:114-121) and FSGS/utils/general_utils.py:157-176 on the device:
+ *   alpha given: d = (depth - min) / (max - min) + 1 * (1 - alpha), every operation rounded to fp32 on its own, min / max
+ *                NaN-propagating as torch's; out_grey_u8 (NULL ok) [H,W,3] = the bytes save_image writes for 1 - d,
+ *                out_composite (NULL ok) fp32 [H,W] = d.
+ *                Without alpha the depth image itself is coloured.
+ *   lo_auto, hi_auto = weighted_percentile(x, ones, [0.5, 99.5]): np.argsort's order (NaN last), acc_w = 1..n, the queries
+ *                p * float32(n / 100) in double, np.interp's statements in double.  A radix select, not a sort: exact.
+ *   lo = lo_auto - eps, hi = hi_auto + eps; eps = float32's epsilon (rules IDENTITY, DNG) or 1e-10 (FSGS)
+ *   curve:       IDENTITY x | DNG -log(x + eps32): the pixel in double, rounded to fp32 once; lo, hi in double |
+ *                FSGS 1 / x + 1e-10: the pixel in fp32, lo and hi in double
+ *   v = nan_to_num(clip((curve(x) - min(lo', hi')) / |hi' - lo'|, 0, 1)) in double, index = trunc(256 v) with 256 -> 255
+ *   out_rgb_u8 [H,W,3] interleaved = row `index` of lut_rgb_u8 [256,3], the caller's table (the byte rule stays on the host)
+ *   out_bounds (NULL ok, device): double[2] = lo, hi before the curve.
+ * All launches go to `stream`; no host synchronisation, integer atomics only: the same bits on every run.
+ * tmp: >= gs_depth_vis_tmp_bytes(H, W) bytes of device scratch, 256-byte aligned; it need not be cleared between calls.
+ * GS_E_SHAPE: H or W < 0, H * W > 2^24 (where float32's cumulative sum of ones stops counting), an unknown rule, tmp_bytes
+ * too small, tmp not 256-byte aligned or an image / out_bounds pointer not aligned to its element; the size query returns 0
+ * for such a shape.  H * W == 0: GS_OK, nothing is launched or written.  GS_E_NULL: depth, lut_rgb_u8, tmp or out_rgb_u8
+ * missing, or out_grey_u8 / out_composite without alpha. */
+#define GS_DEPTH_VIS_IDENTITY 0
+#define GS_DEPTH_VIS_DNG 1
+#define GS_DEPTH_VIS_FSGS 2
+size_t gs_depth_vis_tmp_bytes(int32_t H, int32_t W);
+int gs_depth_vis(const float* depth, const float* alpha /*NULL ok*/, int32_t H, int32_t W, int32_t rule,
+                 const uint8_t* lut_rgb_u8 /*[256,3]*/, void* tmp, size_t tmp_bytes, uint8_t* out_rgb_u8 /*[H,W,3]*/,
+                 uint8_t* out_grey_u8 /*NULL ok*/, float* out_composite /*NULL ok*/, double* out_bounds /*NULL ok*/,
+                 void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

@@ -294,6 +294,8 @@ PROTOTYPES = {
     "resize_bicubic_u8": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _SZ, _P, _P, _P]),
     "eval_ssim_sk_tmp_bytes": (_SZ, [_I32, _I32, _I32]),
     "eval_ssim_sk": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P]),
+    "depth_vis_tmp_bytes": (_SZ, [_I32, _I32]),
+    "depth_vis": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _SZ, _P, _P, _P, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -337,6 +339,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # evaluation from files: Pillow's resize restated in numpy (gsplat_amd/imageio.py, pinned by tests/golden/pil_resize.npz)
                # and skimage's SSIM in float64 numpy (tests/eval_files_reference.py)
                "resize_tmp_bytes", "resize_bicubic_u8", "eval_ssim_sk_tmp_bytes", "eval_ssim_sk",
+               # the coloured depth map: restated in numpy beside its wrapper (gsplat_amd/depth_vis.py, pinned by
+               # tests/golden/depth_vis.npz)
+               "depth_vis_tmp_bytes", "depth_vis",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",
