@@ -1326,6 +1326,52 @@ int gs_depth_vis(const float* depth, const float* alpha /*NULL ok*/, int32_t H, 
                  uint8_t* out_grey_u8 /*NULL ok*/, float* out_composite /*NULL ok*/, double* out_bounds /*NULL ok*/,
                  void* stream);
 
+/* ---- LGDWT-GS's Wavelet Error Field, its heatmap grid and the Charbonnier loss (csrc/gs_wef.hip) ----
+ * LGDWT-GS/utils/loss_utils.py:156-329 and 98-101 on the device, one image per call.
+ * gs_wef_maps: pred, gt [C,H,W] fp32, C in 1..4.  The 2-level Haar bands of pred - gt (the butterfly and repeat-last-sample
+ *   rule of gs_dwt_forward), e = mean_c(scale * b_c^2) (scale 1 at level 1, 4 for LL2, 2 for LH2 / HL2 / HH2), upsampled to
+ *   [H,W] as F.interpolate(mode='bilinear', align_corners=False), n = (u - min) / (max - min + 1e-8f) per map, and the field
+ *   of their mean normalised the same way.  Every operation rounds to fp32 on its own; min and max propagate NaN as torch's
+ *   amin / amax do.
+ *   bands = GS_WEF_LEVEL2: out_maps [4][H][W] = LL2, LH2, HL2, WEF = norm((n_LL2 + n_LH2 + n_HL2) / 3)
+ *   bands = GS_WEF_ALL:    out_maps [9][H][W] = LL1, LH1, HL1, HH1, LL2, LH2, HL2, HH2, COMBINED = norm((their sum in that order) / 8)
+ *   out_bounds (NULL ok, device): float [K + 1][2] = (min, max) of each upsampled map and of the combined field before its
+ *   own normalisation, K = 3 or 8.
+ *   tmp: >= gs_wef_tmp_bytes(C, H, W, bands) bytes of device scratch, 256-byte aligned, not cleared between calls.  After the
+ *   call it starts with the energy planes, each padded to a multiple of 256 bytes: LL2, LH2, HL2, HH2 [ceil(ceil(H/2)/2)]
+ *   [ceil(ceil(W/2)/2)] (HH2's plane is always there, written for GS_WEF_ALL only), then for GS_WEF_ALL LL1, LH1, HL1, HH1
+ *   [ceil(H/2)][ceil(W/2)].
+ *   Six launches on `stream`, no host synchronisation, no atomics: the same bits on every run.
+ * gs_wef_grid: maps [K_total][H][W] -> out_u8 [rows * H][tile_cols * W][3], rows = ceil(n_keys / tile_cols).  Tile idx shows
+ *   maps[order[idx]] at row idx / tile_cols, column idx % tile_cols: x = clamp(v, 0, 1) (NaN -> 0), r = x,
+ *   g = clamp(1 - |x - 0.5| * 2, 0, 1), b = 1 - x, byte = (uint8)(c * 255) truncated.  Unused tiles, and tiles whose order entry
+ *   lies outside [0, K_total), are 0.  order: device int32 [n_keys].
+ *   labels (NULL ok, device): uint8 [n_keys][GS_WEF_LABEL_H][GS_WEF_LABEL_W]; the box of tile idx, GS_WEF_LABEL_W x
+ *   GS_WEF_LABEL_H pixels from the tile's top-left corner and clipped at the image border (not at the tile's), is 255 where
+ *   its label is non-zero and 0 elsewhere; where boxes overlap the highest idx wins (they are drawn in key order).
+ * gs_charbonnier_fwd: out[0] = mean(sqrtf(d * d + eps2)), d = pred - target, eps2 = (float)(epsilon * epsilon); the terms are
+ *   fp32, their sum float64 in a fixed order, divided by n and rounded once.  tmp: >= gs_charbonnier_tmp_bytes(n) bytes, 256-byte
+ *   aligned.  Two launches.
+ * gs_charbonnier_bwd: d_pred[i] = grad_out[0] * d / sqrt(d * d + epsilon^2) / n evaluated in double from the fp32 inputs and
+ *   rounded once, d_target[i] its negative; either may be NULL (not both).  One launch.
+ * GS_E_SHAPE: C outside 1..4, a size below 1, H * W >= 2^31, an unknown band set, tmp_bytes too small, tmp not 256-byte
+ * aligned or another pointer not aligned to its element; the size queries return 0 for such a shape.  GS_E_NULL: a required
+ * pointer missing. */
+#define GS_WEF_LEVEL2 0
+#define GS_WEF_ALL 1
+#define GS_WEF_LABEL_W 121
+#define GS_WEF_LABEL_H 27
+size_t gs_wef_tmp_bytes(int32_t C, int32_t H, int32_t W, int32_t bands);
+int gs_wef_maps(const float* pred, const float* gt, int32_t C, int32_t H, int32_t W, int32_t bands, void* tmp, size_t tmp_bytes,
+                float* out_maps, float* out_bounds /*NULL ok*/, void* stream);
+int gs_wef_grid(const float* maps, int32_t K_total, int32_t H, int32_t W, const int32_t* order /*[n_keys]*/, int32_t n_keys,
+                int32_t tile_cols, const uint8_t* labels /*NULL ok*/, uint8_t* out_u8, void* stream);
+size_t gs_charbonnier_tmp_bytes(int64_t n);
+int gs_charbonnier_fwd(const float* pred, const float* target, int64_t n, double epsilon, void* tmp, size_t tmp_bytes,
+                       float* out /*device [1]*/, void* stream);
+int gs_charbonnier_bwd(const float* pred, const float* target, int64_t n, double epsilon, const float* grad_out /*device [1]*/,
+                       float* d_pred /*NULL ok*/, float* d_target /*NULL ok*/, void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

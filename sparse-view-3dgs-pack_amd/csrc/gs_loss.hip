@@ -13,23 +13,9 @@
 #include <cstdlib>
 
 #include "gs_common.h"
+#include "gs_haar.h"
 #include "gs_prof.h"
 
-#define HC 0.7071067811865476f
-
-struct Bands {
-  float ll, lh, hl, hh;
-};
-__device__ __forceinline__ Bands haar_block(float a, float b, float c, float d) {
-  const float lo_t = HC * a + HC * b, hi_t = HC * a - HC * b;
-  const float lo_b = HC * c + HC * d, hi_b = HC * c - HC * d;
-  Bands r;
-  r.ll = HC * lo_t + HC * lo_b;
-  r.lh = HC * lo_t - HC * lo_b;
-  r.hl = HC * hi_t + HC * hi_b;
-  r.hh = HC * hi_t - HC * hi_b;
-  return r;
-}
 __device__ __forceinline__ void haar_block_adj(float gll, float glh, float ghl, float ghh, float& da, float& db,
                                                float& dc, float& dd) {
   const float dlo_t = HC * gll + HC * glh, dlo_b = HC * gll - HC * glh;
@@ -40,7 +26,6 @@ __device__ __forceinline__ void haar_block_adj(float gll, float glh, float ghl, 
   dd = HC * dlo_b - HC * dhi_b;
 }
 __device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.f) - (x < 0.f)); }
-__device__ __forceinline__ int cdiv2(int n) { return (n + 1) >> 1; }
 
 template <int N>
 __device__ __forceinline__ void block_sum_atomic(float (&v)[N], float* out) {
@@ -448,17 +433,7 @@ __global__ void __launch_bounds__(GS_BLOCK) bilinear_up_kernel(const float* __re
   const int o = blockIdx.x * GS_BLOCK + threadIdx.x;
   if (o >= H * W) return;
   const int x = o % W, y = o / W;
-  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
-  float sy = sh * ((float)y + 0.5f) - 0.5f;
-  if (sy < 0) sy = 0;
-  const int y0 = (int)sy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
-  const float ly1 = sy - (float)y0, ly0 = 1.f - ly1;
-  float sx = sw * ((float)x + 0.5f) - 0.5f;
-  if (sx < 0) sx = 0;
-  const int x0 = (int)sx, x1 = x0 + (x0 < w - 1 ? 1 : 0);
-  const float lx1 = sx - (float)x0, lx0 = 1.f - lx1;
-  out[o] = ly0 * (lx0 * low[(size_t)y0 * w + x0] + lx1 * low[(size_t)y0 * w + x1]) +
-           ly1 * (lx0 * low[(size_t)y1 * w + x0] + lx1 * low[(size_t)y1 * w + x1]);
+  out[o] = bilin_sample(low, w, bilin_tap(y, h, H), bilin_tap(x, w, W));
 }
 // one workgroup per patch
 __global__ void __launch_bounds__(GS_BLOCK) patch_means_kernel(const float* __restrict__ elf, int H, int W, int ps,

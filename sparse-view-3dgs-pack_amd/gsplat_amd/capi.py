@@ -296,6 +296,12 @@ PROTOTYPES = {
     "eval_ssim_sk": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P]),
     "depth_vis_tmp_bytes": (_SZ, [_I32, _I32]),
     "depth_vis": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "wef_tmp_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
+    "wef_maps": (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P, _P]),
+    "wef_grid": (C.c_int, [_P, _I32, _I32, _I32, _P, _I32, _I32, _P, _P, _P]),
+    "charbonnier_tmp_bytes": (_SZ, [_I64]),
+    "charbonnier_fwd": (C.c_int, [_P, _P, _I64, C.c_double, _P, _SZ, _P, _P]),
+    "charbonnier_bwd": (C.c_int, [_P, _P, _I64, C.c_double, _P, _P, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -342,6 +348,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # the coloured depth map: restated in numpy beside its wrapper (gsplat_amd/depth_vis.py, pinned by
                # tests/golden/depth_vis.npz)
                "depth_vis_tmp_bytes", "depth_vis",
+               # the Wavelet Error Field, its heatmap grid and the Charbonnier loss: restated in torch beside their wrapper
+               # (gsplat_amd/wef.py, pinned by tests/golden/wef_maps.npz)
+               "wef_tmp_bytes", "wef_maps", "wef_grid", "charbonnier_tmp_bytes", "charbonnier_fwd", "charbonnier_bwd",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",

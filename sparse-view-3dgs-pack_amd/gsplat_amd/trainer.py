@@ -1712,6 +1712,37 @@ class Trainer:
             for k, v in saved.items():
                 setattr(be, k, v)
 
+    def wef_report(self, camera=0, bands="level2", path=None, titled=False, tile_cols=3):
+        """The Wavelet Error Field of one training camera (gsplat_amd.wef): {"LL2", "LH2", "HL2", "WEF"} (bands="level2") or the
+        eight bands and "COMBINED" (bands="all") of clamp(render, 0, 1) against the camera's ground truth, [1,1,H,W] each, plus
+        "grid": their heatmap grid, uint8 [rows * H, tile_cols * W, 3] (titled: with the keys stamped on), written as a PNG
+        when `path` is given.  The view is rendered as evaluate() renders: sync() first, the plain forward under no_grad with
+        its own camera key, the backend's records restored - no optimizer counter, running mean, random stream or per-camera
+        entry is touched.  Trainers with an evaluate() of their own (DNGaussian's) render differently and raise."""
+        from . import wef
+        if bands not in ("level2", "all"):
+            raise ValueError("wef_report: bands is 'level2' or 'all' (got %r)" % (bands,))
+        if type(self).evaluate is not Trainer.evaluate:
+            raise NotImplementedError("wef_report renders as Trainer.evaluate does; %s renders its views differently" % type(self).__name__)
+        self.sync()
+        ci = int(camera)
+        be = self._backend()
+        saved = {k: getattr(be, k) for k in self._EVAL_KEEPS if be is not None and hasattr(be, k)}
+        try:
+            with torch.no_grad():
+                img = render(self.cameras[ci], self.model, self.Rasterizer, self.Settings, self.bg, filter_as_indices=None,
+                             clamp=False, camera_key=("trainer", self.uid, "eval", ci))["render"].clamp(0, 1)
+        finally:
+            for k, v in saved.items():
+                setattr(be, k, v)
+        gt = self.gts[ci].to(img.device)
+        maps = wef.compute_wef_all_subbands(img, gt) if bands == "all" else wef.compute_wef_maps(img, gt)
+        grid = (wef.make_wef_grid_image_titled if titled else wef.make_wef_grid_image)(maps, list(maps), tile_cols=tile_cols)
+        if path is not None:
+            from .imageio import write_png
+            write_png(path, grid)
+        return dict(maps, grid=grid)
+
     # -- DNGaussian's prunes between iterations (train_llff.py:206-213, 264-274): a re-layout each, so both are preceded by what
     # the densification branch of train_iteration does before it touches the model
     def _before_relayout(self, on_device, opt):
