@@ -1372,6 +1372,50 @@ int gs_charbonnier_fwd(const float* pred, const float* target, int64_t n, double
 int gs_charbonnier_bwd(const float* pred, const float* target, int64_t n, double epsilon, const float* grad_out /*device [1]*/,
                        float* d_pred /*NULL ok*/, float* d_target /*NULL ok*/, void* stream);
 
+/* ---- depth priors from files: depth_params.json's fit and the camera's inverse-depth map (csrc/gs_depth_priors.hip) ----
+ * gs_depth_scales: gaussian-splatting/utils/make_depth_scale.py:8-64 for n_images images in ONE launch, one workgroup per
+ *   image.  Image i owns the observations [seg[i], seg[i + 1]) of obs_ids / obs_xy (seg: device int64 [n_images + 1], ascending,
+ *   seg[n_images] <= n_obs).  Per observation, in double, one rounding per operation:
+ *     used  = 0 <= id < n_table                       (a row of the dense table that no point fills is zeros and is used)
+ *     z     = ((X r20 + Y r21) + Z r22) + t2,  inv = 1 / z          (X, Y, Z) = table[id]; the script reads no other row of R
+ *     mx    = (float)(x s), my = (float)(y s)          s = map rows / camera height
+ *     valid = used && mx >= 0 && my >= 0 && mx < wlim && my < hlim && inv > 0     the four map tests in fp32
+ *     mono  = the map sampled at (mx, my): each coordinate rounded half-to-even to 2^-coord_bits of a pixel
+ *             (i = rint(x 2^bits), cell = i >> bits, f = (i & (2^bits - 1)) / 2^bits; coord_bits < 0: cell = floor(x), f = x - cell),
+ *             weights (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx and ((w00 v00 + w01 v01) + w10 v10) + w11 v11 with every
+ *             multiply and add rounded to fp32, cell indices clamped to the map.  A map sample is value / 65536 (uint16 or fp32).
+ *   cams: device double [n_images][8] = r20, r21, r22, t2, s, wlim, hlim, 0 (wlim / hlim hold fp32 values: (float)(width s), ...).
+ *   maps: device array of n_images device pointers; map_hw: device int32 [n_images][2] = rows, columns (each 1 .. 2^20).
+ *   map_dtype: GS_DEPTH_MAP_U16 or GS_DEPTH_MAP_F32, for every map of the call.
+ *   n_valid > 10 and (max - min of inv over the USED observations) > 1e-3, else scale = offset = 0.  Otherwise the medians of
+ *   inv (double) and mono (fp32) over the valid observations by radix select (both middle elements when the count is even:
+ *   (a + b) / 2 in the sequence's own precision), the mean absolute deviations as float64 sums in a fixed order (per-lane
+ *   strided partials, a fixed tree) divided by n_valid, scale = s_colmap / s_mono, offset = t_colmap - t_mono scale.
+ *   out: device double [n_images][8] = scale, offset, n_valid, t_colmap, s_colmap, t_mono, s_mono, max - min (the four
+ *   statistics are 0 where the gate fails).
+ *   tmp: >= gs_depth_scales_tmp_bytes(n_obs) bytes of device scratch, 256-byte aligned, not cleared between calls.
+ *   Integer atomics in LDS only, no host synchronisation: the same bits on every run.
+ * gs_invdepth_prepare: gaussian-splatting/scene/cameras.py:60-78 for one map, one launch.  src [H][W] uint16 or fp32; per output
+ *   pixel of [H2][W2]: value / divisor (fp32 division), bilinear resize (fx = (float)((dx + 0.5) * ((double)W / W2) - 0.5),
+ *   sx = floor(fx), fx -= sx, sx < 0 -> (0, 0), sx >= W - 1 -> (W - 1, 0); horizontally a0 S0 + a1 S1 with a0 = 1 - fx, a1 = fx,
+ *   then vertically the same, every operation rounded to fp32; equal sizes copy), negatives to 0, then with apply_scale != 0
+ *   x * scale rounded, + offset rounded (never fused).  out_mask (NULL ok) [H2][W2] = mask_value.
+ * GS_E_SHAPE: a count or size below its minimum or above its maximum (n_images, n_obs, n_table < 0; H, W, H2, W2 outside
+ * 1 .. 2^15), an unknown dtype, coord_bits > 10, tmp_bytes too small, tmp not 256-byte aligned, a pointer not aligned to its
+ * element.  n_images == 0: GS_OK, nothing launched.  GS_E_NULL: a required pointer missing (obs_* and points may be NULL when
+ * n_obs == 0 / n_table == 0). */
+#define GS_DEPTH_MAP_U16 0
+#define GS_DEPTH_MAP_F32 1
+size_t gs_depth_scales_tmp_bytes(int64_t n_obs);
+int gs_depth_scales(const double* points /*[n_table,3]*/, int64_t n_table, const int64_t* obs_ids /*[n_obs]*/,
+                    const double* obs_xy /*[n_obs,2]*/, int64_t n_obs, const int64_t* seg /*[n_images+1]*/,
+                    const double* cams /*[n_images,8]*/, const void* const* maps /*[n_images]*/, const int32_t* map_hw /*[n_images,2]*/,
+                    int32_t map_dtype, int32_t coord_bits, int32_t n_images, void* tmp, size_t tmp_bytes,
+                    double* out /*[n_images,8]*/, void* stream);
+int gs_invdepth_prepare(const void* src, int32_t src_dtype, int32_t H, int32_t W, int32_t H2, int32_t W2, float divisor,
+                        int32_t apply_scale, float scale, float offset, float mask_value, float* out_invdepth /*[H2,W2]*/,
+                        float* out_mask /*NULL ok*/, void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

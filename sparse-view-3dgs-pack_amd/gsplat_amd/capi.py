@@ -302,6 +302,9 @@ PROTOTYPES = {
     "charbonnier_tmp_bytes": (_SZ, [_I64]),
     "charbonnier_fwd": (C.c_int, [_P, _P, _I64, C.c_double, _P, _SZ, _P, _P]),
     "charbonnier_bwd": (C.c_int, [_P, _P, _I64, C.c_double, _P, _P, _P, _P]),
+    "depth_scales_tmp_bytes": (_SZ, [_I64]),
+    "depth_scales": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P]),
+    "invdepth_prepare": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.c_float, _I32, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -351,6 +354,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # the Wavelet Error Field, its heatmap grid and the Charbonnier loss: restated in torch beside their wrapper
                # (gsplat_amd/wef.py, pinned by tests/golden/wef_maps.npz)
                "wef_tmp_bytes", "wef_maps", "wef_grid", "charbonnier_tmp_bytes", "charbonnier_fwd", "charbonnier_bwd",
+               # depth priors from files: the host numpy path beside the wrapper is the arbiter (gsplat_amd/depth_priors.py,
+               # restated with float64 forms in tests/depth_prior_reference.py)
+               "depth_scales_tmp_bytes", "depth_scales", "invdepth_prepare",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",

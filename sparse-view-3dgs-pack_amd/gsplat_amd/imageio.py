@@ -2,6 +2,7 @@
 torchvision's save_image byte rule, and PIL.Image.resize's default filter on 8-bit images, bit for bit.
 
   write_png / read_png    8-bit grey, grey + alpha, RGB, RGBA; non-interlaced.  16-bit, palette and interlaced files raise.
+  write_png16 / read_png16  the same four colour types at 16 bits per sample (the depth priors' files, gsplat_amd/depth_priors.py)
   save_image_bytes        the uint8 [H,W,C] image torchvision.utils.save_image writes for a [C,H,W] float tensor
                           (LGDWT-GS/render.py:45-46): mul(255).add(0.5).clamp(0, 255).to(uint8), one channel written as three
   resize_u8               Image.resize((W2, H2)) of a mode-L / mode-RGB image (DNGaussian/metrics_dtu.py:37-39): the antialiased
@@ -103,21 +104,20 @@ def _unfilter(raw, H, stride, bpp):
     return out
 
 
-def read_png(path):
-    """-> uint8 numpy [H,W,C], C = 1 (grey), 2 (grey + alpha), 3 (RGB) or 4 (RGBA).  8-bit, non-interlaced files only:
-    16-bit (or 1 / 2 / 4-bit), palette and interlaced files raise ValueError."""
+def _png_parse(path, who):
+    """-> (the IHDR fields, the concatenated IDAT bytes) of a PNG file whose chunks all pass their checksum"""
     with open(path, "rb") as fp:
         data = fp.read()
     if data[:8] != _SIG:
-        raise ValueError("read_png: %s is not a PNG file" % path)
+        raise ValueError("%s: %s is not a PNG file" % (who, path))
     pos, ihdr, idat, ended = 8, None, [], False
     while pos + 8 <= len(data) and not ended:
         n, tag = struct.unpack(">I4s", data[pos:pos + 8])
         body = data[pos + 8:pos + 8 + n]
         if len(body) != n or pos + 12 + n > len(data):
-            raise ValueError("read_png: %s is truncated" % path)
+            raise ValueError("%s: %s is truncated" % (who, path))
         if struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
-            raise ValueError("read_png: %s: bad checksum in chunk %r" % (path, tag))
+            raise ValueError("%s: %s: bad checksum in chunk %r" % (who, path, tag))
         pos += 12 + n
         if tag == b"IHDR":
             ihdr = struct.unpack(">IIBBBBB", body)
@@ -126,7 +126,14 @@ def read_png(path):
         elif tag == b"IEND":
             ended = True
     if ihdr is None or not idat or not ended:
-        raise ValueError("read_png: %s has no IHDR / IDAT / IEND" % path)
+        raise ValueError("%s: %s has no IHDR / IDAT / IEND" % (who, path))
+    return ihdr, b"".join(idat)
+
+
+def read_png(path):
+    """-> uint8 numpy [H,W,C], C = 1 (grey), 2 (grey + alpha), 3 (RGB) or 4 (RGBA).  8-bit, non-interlaced files only:
+    16-bit (or 1 / 2 / 4-bit), palette and interlaced files raise ValueError (read_png16 reads 16-bit files)."""
+    ihdr, idat = _png_parse(path, "read_png")
     W, H, depth, ctype, comp, filt, interlace = ihdr
     if ctype == 3:
         raise ValueError("read_png: %s is a palette image - not supported (8-bit grey, grey + alpha, RGB, RGBA only)" % path)
@@ -137,10 +144,60 @@ def read_png(path):
     if ctype not in _CHANNELS or comp != 0 or filt != 0 or W < 1 or H < 1:
         raise ValueError("read_png: %s: unsupported header %r" % (path, ihdr))
     Cn = _CHANNELS[ctype]
-    raw = zlib.decompress(b"".join(idat))
+    raw = zlib.decompress(idat)
     if len(raw) != H * (1 + W * Cn):
         raise ValueError("read_png: %s: %d bytes of image data for %d x %d x %d" % (path, len(raw), H, W, Cn))
     return _unfilter(raw, H, W * Cn, Cn).reshape(H, W, Cn)
+
+
+def read_png16(path):
+    """-> uint16 numpy [H,W] (grey) or [H,W,C], C = 2 (grey + alpha), 3 (RGB) or 4 (RGBA): what cv2.imread(path, -1) hands
+    the reference's depth readers for a grey file.  16-bit samples are big-endian in the file; the five row filters work on
+    BYTES and take their "left" byte one whole pixel back, 2 C bytes at 16 bits.  An 8-bit file comes back as uint16 holding
+    the bytes' values, unscaled (as cv2.imread(-1).astype(float32) keeps them).  Palette, interlaced and 1 / 2 / 4-bit files
+    raise ValueError.  Channels stay in file order (R, G, B): cv2 would hand B, G, R."""
+    ihdr, idat = _png_parse(path, "read_png16")
+    W, H, depth, ctype, comp, filt, interlace = ihdr
+    if ctype == 3:
+        raise ValueError("read_png16: %s is a palette image - not supported" % path)
+    if depth not in (8, 16):
+        raise ValueError("read_png16: %s has %d bits per sample - 16-bit (or 8-bit) files only" % (path, depth))
+    if interlace != 0:
+        raise ValueError("read_png16: %s is interlaced (Adam7) - not supported" % path)
+    if ctype not in _CHANNELS or comp != 0 or filt != 0 or W < 1 or H < 1:
+        raise ValueError("read_png16: %s: unsupported header %r" % (path, ihdr))
+    Cn, nb = _CHANNELS[ctype], depth // 8
+    raw = zlib.decompress(idat)
+    if len(raw) != H * (1 + W * Cn * nb):
+        raise ValueError("read_png16: %s: %d bytes of image data for %d x %d x %d x %d" % (path, len(raw), H, W, Cn, nb))
+    rows = _unfilter(raw, H, W * Cn * nb, Cn * nb)
+    out = rows.astype(np.uint16) if nb == 1 else np.ascontiguousarray(rows).view(">u2").astype(np.uint16)
+    return out.reshape(H, W) if Cn == 1 else out.reshape(H, W, Cn)
+
+
+def png16_bytes(u16, level=6):
+    """uint16 [H,W], [H,W,1], [H,W,2], [H,W,3] or [H,W,4] -> the bytes of a 16-bit, non-interlaced PNG (filter type 0)"""
+    if torch.is_tensor(u16):
+        u16 = u16.detach().cpu().numpy()
+    u16 = np.asarray(u16)
+    if u16.dtype != np.uint16:
+        raise ValueError("png16_bytes: uint16 only (got %s)" % u16.dtype)
+    if u16.ndim == 2:
+        u16 = u16[:, :, None]
+    if u16.ndim != 3 or u16.shape[2] not in _COLOUR_TYPE or u16.shape[0] < 1 or u16.shape[1] < 1:
+        raise ValueError("png16_bytes: [H,W] or [H,W,1..4] of at least one pixel (got %s)" % (u16.shape,))
+    H, W, Cn = u16.shape
+    rows = np.zeros((H, 1 + 2 * W * Cn), dtype=np.uint8)
+    rows[:, 1:] = np.ascontiguousarray(u16.astype(">u2")).view(np.uint8).reshape(H, 2 * W * Cn)
+    ihdr = struct.pack(">IIBBBBB", W, H, 16, _COLOUR_TYPE[Cn], 0, 0, 0)
+    return _SIG + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", zlib.compress(rows.tobytes(), level)) + _chunk(b"IEND", b"")
+
+
+def write_png16(path, u16):
+    """Write uint16 [H,W] or [H,W,1..4] (tensor or array) as a 16-bit, non-interlaced PNG: the form of the depth files."""
+    data = png16_bytes(u16)
+    with open(path, "wb") as fp:
+        fp.write(data)
 
 
 # ------------------------------------------------------------------------------------------------ save_image's bytes

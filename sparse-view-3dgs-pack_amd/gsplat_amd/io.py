@@ -271,16 +271,18 @@ def read_extrinsics_binary(path):
     return images
 
 
-def read_points3D_binary(path):
-    """points3D.bin (colmap_loader.py:113-141) -> (xyz [N,3] f64, rgb [N,3], error [N,1]); tracks are skipped."""
+def read_points3D_binary(path, with_ids=False):
+    """points3D.bin (colmap_loader.py:113-141) -> (xyz [N,3] f64, rgb [N,3], error [N,1]); tracks are skipped.
+    with_ids: also the points' POINT3D_IDs, int64 [N] (what the images' point3D_ids refer to), as a fourth entry."""
     with open(path, "rb") as f:
         n = _unpack(f, "Q")[0]
         xyz, rgb, err = np.empty((n, 3)), np.empty((n, 3)), np.empty((n, 1))
+        ids = np.empty((n,), dtype=np.int64)
         for i in range(n):
             p = _unpack(f, "QdddBBBd")
-            xyz[i], rgb[i], err[i] = p[1:4], p[4:7], p[7]
+            ids[i], xyz[i], rgb[i], err[i] = p[0], p[1:4], p[4:7], p[7]
             f.seek(8 * _unpack(f, "Q")[0], os.SEEK_CUR)
-    return xyz, rgb, err
+    return (xyz, rgb, err, ids) if with_ids else (xyz, rgb, err)
 
 
 def _data_lines(path):
@@ -330,13 +332,16 @@ def _data_lines_keep_empty(path):
             pose_next = not pose_next
 
 
-def read_points3D_text(path):
+def read_points3D_text(path, with_ids=False):
     """points3D.txt (colmap_loader.py:83-110): `id x y z r g b error track...`.  Shapes / dtypes as the reference's
-    text reader returns them (rgb int64 [N,3], error [N] - its binary reader gives float64 [N,3] and [N,1])."""
+    text reader returns them (rgb int64 [N,3], error [N] - its binary reader gives float64 [N,3] and [N,1]).
+    with_ids: also the points' POINT3D_IDs, int64 [N], as a fourth entry."""
     rows = [line.split() for line in _data_lines(path)]
     xyz = np.array([[float(v) for v in r[1:4]] for r in rows]).reshape(-1, 3)
     rgb = np.array([[int(v) for v in r[4:7]] for r in rows], dtype=np.int64).reshape(-1, 3)
     err = np.array([float(r[7]) for r in rows])
+    if with_ids:
+        return xyz, rgb, err, np.array([int(r[0]) for r in rows], dtype=np.int64)
     return xyz, rgb, err
 
 

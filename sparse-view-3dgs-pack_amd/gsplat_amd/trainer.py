@@ -1867,6 +1867,17 @@ class Trainer:
                       clamp=not fused, fused=True, use_trained_exp=m.exposure is not None and not self._use_stage, camera_index=ci,
                       raw_activations=raw, camera_key=("trainer", self.uid, ci))
 
+    def load_depth_priors(self, keys, depths_dir, depth_params=None, resolutions=None, nerf_synthetic=False):
+        """Fill depth_priors from a folder of 16-bit inverse-depth PNGs (gsplat_amd/depth_priors.py::load_depth_priors): keys = per
+        camera the image's name without extension, depth_params = read_depth_params' dict; resolutions default to the ground
+        truths' (W, H).  The maps land on the ground truths' device."""
+        from .depth_priors import load_depth_priors
+        if resolutions is None:
+            resolutions = [(int(g.shape[-1]), int(g.shape[-2])) for g in self.gts]
+        self.depth_priors = load_depth_priors(keys, depths_dir, depth_params, resolutions, nerf_synthetic=nerf_synthetic,
+                                              device=self.gts[0].device)
+        return self.depth_priors
+
     def _depth_prior(self, ci):
         """(mono_invdepth, depth_mask) of camera ci when the depth term is on for it (train.py:206), else None"""
         if self.depth_priors is None or not self.depth_l1_weight > 0:
