@@ -1297,6 +1297,45 @@ size_t gs_eval_ssim_sk_tmp_bytes(int32_t C, int32_t H, int32_t W);
 int gs_eval_ssim_sk(const float* render, const float* gt, const float* mask /*NULL unless GS_EVAL_MASK_DTU*/, int32_t C,
                     int32_t H, int32_t W, int32_t flags, void* tmp, size_t tmp_bytes, double* out /*device*/, void* stream);
 
+/* ---- LPIPS, net_type='vgg', version 0.1, forward only (csrc/gs_lpips.hip) ----
+ * Additive entries (GS_ABI_VERSION unchanged).  lpipsPyTorch/modules/lpips.py:30-36 of render against gt, both [C,H,W] fp32 of
+ * which the first three channels are used, after gs_eval_metrics's pixel transform (same flags, same order, the one
+ * implementation) and the reference's z_score on the image as it is in [0, 1].  The weights are the caller's:
+ *   packed_w[13]  the thirteen 3 x 3 convolutions of torchvision's vgg16().features up to relu5_3, each repacked ONCE by
+ *                 gs_lpips_pack_weights from torch's [Cout][Cin][3][3] into gs_lpips_packed_floats(Cin, Cout) floats
+ *                 ([Cin, padded to 4 for Cin = 3][9][Cout]; 16-byte aligned);
+ *   bias[13]      their biases, [Cout] fp32;
+ *   lin[5]        the 1 x 1 "lin" weights of the five taps (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3), [C] FLOAT64
+ *                 (the fp32 weights widened).
+ * The three are HOST arrays of device pointers.  out[6] doubles in device memory: the five per-tap terms, then their sum in
+ * tap order.  The convolutions run on the f32 MFMA in one fixed K order; everything from the fp32 features on is float64
+ * summed in one fixed order: the same bits on every call, and an image's features do not depend on its slot of the pair.  No
+ * atomics, no host synchronisation, no device-to-host copy; every word of tmp is written before it is read.
+ * tmp: >= gs_lpips_tmp_bytes(H, W) bytes of device scratch (two activation buffers of 2 x 64 x H x W fp32 and the distance's
+ * partials), 256-byte aligned.
+ * GS_E_NULL: a required pointer is missing (mask only with GS_EVAL_MASK_DTU); GS_E_SHAPE: C outside 3..4, H or W below 16 (the
+ * fifth tap would be empty; torch raises there too), H * W > 2^24, unknown flag bits or a packed weight off 16 bytes;
+ * GS_E_SCRATCH: tmp_bytes too small.  gs_lpips_tmp_bytes returns 0 for such a size.
+ *
+ * The stages on their own, launched exactly as gs_lpips_vgg launches them (the tests' handle on each):
+ *   gs_lpips_conv3x3_relu  y [N][Cout][H][W] = relu(conv3x3(x [N][Cin][H][W], padding 1) + bias), (Cin, Cout) one of VGG16's
+ *                          eight pairs 3-64, 64-64, 64-128, 128-128, 128-256, 256-256, 256-512, 512-512 (else GS_E_SHAPE)
+ *   gs_lpips_maxpool2      y [NC][H/2][W/2] = max over 2 x 2, stride 2, an odd last row or column dropped; H, W >= 2
+ *   gs_lpips_distance      out[0] = mean over the pixels of sum_c lin[c] (x_c / (|x| + 1e-10) - y_c / (|y| + 1e-10))^2 of two
+ *                          [C][H][W] fp32 feature maps; tmp >= gs_lpips_distance_tmp_bytes(H, W) */
+int64_t gs_lpips_packed_floats(int32_t Cin, int32_t Cout);
+int gs_lpips_pack_weights(const float* w /*[Cout][Cin][3][3]*/, int32_t Cin, int32_t Cout, float* packed, void* stream);
+size_t gs_lpips_tmp_bytes(int32_t H, int32_t W);
+int gs_lpips_vgg(const float* render, const float* gt, const float* mask /*NULL unless GS_EVAL_MASK_DTU*/, int32_t C, int32_t H,
+                 int32_t W, int32_t flags, const float* const* packed_w /*host [13]*/, const float* const* bias /*host [13]*/,
+                 const double* const* lin /*host [5]*/, void* tmp, size_t tmp_bytes, double* out /*[6], device*/, void* stream);
+int gs_lpips_conv3x3_relu(const float* x, const float* packed_w, const float* bias, int32_t N, int32_t Cin, int32_t Cout,
+                          int32_t H, int32_t W, float* y, void* stream);
+int gs_lpips_maxpool2(const float* x, int64_t NC, int32_t H, int32_t W, float* y, void* stream);
+size_t gs_lpips_distance_tmp_bytes(int32_t H, int32_t W);
+int gs_lpips_distance(const float* fx, const float* fy, const double* lin, int32_t C, int32_t H, int32_t W, void* tmp,
+                      size_t tmp_bytes, double* out /*device*/, void* stream);
+
 /* ---- the turbo-coloured depth map of the render stage (csrc/gs_depth_vis.hip) ----
  * DNGaussian/render.py:121,127-130 (and spiral.py:114-121) and FSGS/utils/general_utils.py:157-176 on the device:
  *   alpha given: d = (depth - min) / (max - min) + 1 * (1 - alpha), every operation rounded to fp32 on its own, min / max

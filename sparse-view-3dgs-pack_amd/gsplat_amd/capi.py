@@ -294,6 +294,14 @@ PROTOTYPES = {
     "resize_bicubic_u8": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _P, _SZ, _P, _P, _P]),
     "eval_ssim_sk_tmp_bytes": (_SZ, [_I32, _I32, _I32]),
     "eval_ssim_sk": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _SZ, _P, _P]),
+    "lpips_packed_floats": (C.c_int64, [_I32, _I32]),
+    "lpips_pack_weights": (C.c_int, [_P, _I32, _I32, _P, _P]),
+    "lpips_tmp_bytes": (_SZ, [_I32, _I32]),
+    "lpips_vgg": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _SZ, _P, _P]),
+    "lpips_conv3x3_relu": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    "lpips_maxpool2": (C.c_int, [_P, _I64, _I32, _I32, _P, _P]),
+    "lpips_distance_tmp_bytes": (_SZ, [_I32, _I32]),
+    "lpips_distance": (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P]),
     "depth_vis_tmp_bytes": (_SZ, [_I32, _I32]),
     "depth_vis": (C.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _SZ, _P, _P, _P, _P, _P]),
     "wef_tmp_bytes": (_SZ, [_I32, _I32, _I32, _I32]),
@@ -348,6 +356,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # evaluation from files: Pillow's resize restated in numpy (gsplat_amd/imageio.py, pinned by tests/golden/pil_resize.npz)
                # and skimage's SSIM in float64 numpy (tests/eval_files_reference.py)
                "resize_tmp_bytes", "resize_bicubic_u8", "eval_ssim_sk_tmp_bytes", "eval_ssim_sk",
+               # LPIPS (VGG16): restated in torch (tests/lpips_reference.py, pinned by tests/golden/lpips.npz)
+               "lpips_packed_floats", "lpips_pack_weights", "lpips_tmp_bytes", "lpips_vgg", "lpips_conv3x3_relu",
+               "lpips_maxpool2", "lpips_distance_tmp_bytes", "lpips_distance",
                # the coloured depth map: restated in numpy beside its wrapper (gsplat_amd/depth_vis.py, pinned by
                # tests/golden/depth_vis.npz)
                "depth_vis_tmp_bytes", "depth_vis",

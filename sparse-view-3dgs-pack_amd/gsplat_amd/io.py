@@ -503,8 +503,8 @@ def write_cameras_json(path, cam_infos):
 # ------------------------------------------------------------------------------------------------ evaluation results
 def write_results_json(model_path, method, result):
     """results.json = {method: {"SSIM": ..., "PSNR": ...}} and per_view.json = {method: {"SSIM": {name: v}, ...}} under
-    model_path, in the nesting of metrics.py:85-88 (json.dump(..., indent=True)).  The keys are those of `result`: no
-    LPIPS key is written (absent, not zero); L1 is this package's addition."""
+    model_path, in the nesting of metrics.py:85-88 (json.dump(..., indent=True)).  The keys are those of `result`: the
+    LPIPS key is written when the evaluation was given LPIPS weights (else absent, not zero); L1 is this package's addition."""
     per = result["per_view"]
     full = {k: v for k, v in result.items() if k != "per_view"}
     os.makedirs(model_path, exist_ok=True)

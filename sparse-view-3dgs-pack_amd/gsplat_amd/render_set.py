@@ -14,8 +14,9 @@ scored on the device.
                       mask resized to a quarter (size // 4), render and ground truth resized to the mask's size - PIL's
                       Image.resize restated in csrc/gs_eval_files.hip - to_tensor, the blend to white, PSNR over mask == 1.
 
-The renders/ and gt/ folders are also the hand-off to LPIPS, which this package does not compute, and the way to compare a
-run of the reference image by image.  Divergences, raised or stated here:
+With lpips = the LpipsWeights (gsplat_amd/lpips.py) evaluate_dir adds the LPIPS key, metrics.py:74,83-86's
+lpips(render, gt, net_type='vgg'); with mask_dir it is the LPIPS of the pair blended to white (metrics_dtu.py:42-43,98).  The
+renders/ and gt/ folders remain the way to compare a run of the reference image by image.  Divergences, raised or stated here:
   * no video container is written (spiral.py:123-125's ffmpeg calls, render.py:66-81's cv2.VideoWriter): neither ffmpeg nor
     cv2 is a dependency; the numbered frames are what both would encode.
   * FSGS names a render set's files by view.image_name; here they are numbered in the order given unless a frame carries
@@ -25,7 +26,7 @@ run of the reference image by image.  Divergences, raised or stated here:
   * views are scored in sorted file order (the reference in os.listdir's order; the means do not depend on it).
   * results.json / per_view.json are written through io.write_results_json as it stands: one method per file, so with
     several method folders the files hold the last one in sorted order; the returned dictionary holds all of them.
-  * no LPIPS key; L1 is added (evaluate.py)."""
+  * the LPIPS key only on request (its weights are the user's files); L1 is added (evaluate.py)."""
 import os
 
 import numpy as np
@@ -147,9 +148,10 @@ def _mask_plane(path):
     return np.ascontiguousarray(m[:, :, :1])
 
 
-def evaluate_dir(model_path, name="test", mask_dir=None, ssim_sk=False, device="cuda"):
+def evaluate_dir(model_path, name="test", mask_dir=None, ssim_sk=False, device="cuda", lpips=None):
     """-> {method: Evaluator.result(names)} for every method folder (ours_<iteration>) under <model_path>/<name>, and
-    results.json / per_view.json under model_path.  One read-back per method folder.  All views of a method share one size."""
+    results.json / per_view.json under model_path.  One read-back per method folder.  All views of a method share one size.
+    lpips: the LpipsWeights; results.json and per_view.json then carry the LPIPS key."""
     device = torch.device(device)
     test_dir = os.path.join(model_path, name)
     out = {}
@@ -179,7 +181,7 @@ def evaluate_dir(model_path, name="test", mask_dir=None, ssim_sk=False, device="
             if r.shape != g.shape:
                 raise ValueError("evaluate_dir: %s: render %s and gt %s differ in shape" % (fname, tuple(r.shape), tuple(g.shape)))
             if ev is None:
-                ev = evaluate.Evaluator(len(names), r.shape[0], r.shape[1], r.shape[2], device, ssim_sk=ssim_sk)
+                ev = evaluate.Evaluator(len(names), r.shape[0], r.shape[1], r.shape[2], device, ssim_sk=ssim_sk, lpips=lpips)
             ev.add(i, r, g, mask=mask)   # (the files' values are bytes / 255 already: no clamp, no second quantisation)
         out[method] = ev.result(names)
         write_results_json(model_path, method, out[method])

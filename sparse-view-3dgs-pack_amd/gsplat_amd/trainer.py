@@ -1691,7 +1691,7 @@ class Trainer:
 
     def evaluate(self, cameras=None, gts=None, **kw):
         """PSNR / SSIM / L1 of the trainer's model over a test set (default: its own cameras and ground truth) ->
-        gsplat_amd.evaluate.evaluate_views' result; kw: names, quantise, clamp, masks.
+        gsplat_amd.evaluate.evaluate_views' result; kw: names, quantise, clamp, masks, lpips (the LpipsWeights, for "LPIPS").
 
         Training state is left alone, and this is how: the pending verdict of the last step is settled first (sync);
         every view is rendered through the PLAIN forward under no_grad, named ("trainer", uid, "eval", i) with
@@ -3176,10 +3176,10 @@ class TrainerDNG(Trainer):
             self._rng.setstate(state["rng"])
         self._stack = list(state["stack"])
 
-    def evaluate(self, cameras=None, gts=None, names=None, quantise=True, clamp=True, masks=None):
+    def evaluate(self, cameras=None, gts=None, names=None, quantise=True, clamp=True, masks=None, lpips=None):
         """PSNR / SSIM / L1 over a test set (default: the trainer's cameras and ground truth), every view rendered through
         render_dng under no_grad -> gsplat_amd.evaluate.Evaluator.result(names).  No optimizer counter, statistic or random
-        stream is touched."""
+        stream is touched.  lpips: the LpipsWeights, for the "LPIPS" entries."""
         from .evaluate import Evaluator
         cameras = self.cameras if cameras is None else cameras
         gts = self.gts if gts is None else gts
@@ -3188,7 +3188,7 @@ class TrainerDNG(Trainer):
             for i, (cam, gt) in enumerate(zip(cameras, gts)):
                 img = self._render(cam)["render"]
                 if ev is None:
-                    ev = Evaluator(len(cameras), img.shape[0], img.shape[1], img.shape[2], img.device)
+                    ev = Evaluator(len(cameras), img.shape[0], img.shape[1], img.shape[2], img.device, lpips=lpips)
                 ev.add(i, img, gt, mask=None if masks is None else masks[i], clamp=clamp, quantise=quantise)
         return ev.result(names)
 
