@@ -25,7 +25,13 @@
 // their own in front of the same gather (gs_prune_plan / gs_prune_emit).
 //
 // The second half of the file is FSGS's densification (FSGS/scene/gaussian_model.py:424-491, the device form of
-// GaussianModelLite.densify_and_prune_fsgs): the same building blocks, but its stages hang on two kNN searches (see there).
+// GaussianModelLite.densify_and_prune_fsgs): its stages hang on two kNN searches (see there).
+//
+// What the rules share stands once, in front of the kernels: dn_block_ranks (every plan and emit kernel's ballot / popcount
+// ranks), dn_row_measures (both plans' per-row measures; each rule sets its own flag bits from them), dn_rotation /
+// dn_sample_centre / dn_put_row / dn_put_samples (both emits), and ONE gather body, gather_rows<WC, PROX> in gather_block<PROX>:
+// densify_gather_kernel (PROX off: no proximity branch, no neighbour-kind array) and fsgs_gather_kernel are its two
+// instantiations, and dn_gather builds and checks the field table of both entry points.
 #include <math.h>
 
 #include "gs_common.h"
@@ -59,6 +65,94 @@ static inline DensifyTmp dn_tmp_view(void* buf, size_t P) {
   return t;
 }
 
+// In-block exclusive ranks of K predicates - ballot / popcount inside the wave, the waves' counts through LDS - and the block's
+// counts.  Every thread of the workgroup calls it (it synchronises), or none: an early return in front of it must be uniform
+// over the workgroup.
+template <int K>
+static __device__ __forceinline__ void dn_block_ranks(const bool* c, uint32_t (*s_cnt)[DN_NC], uint32_t* rank, uint32_t* total) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const unsigned long long b = __ballot(c[k]);
+    rank[k] = (uint32_t)__popcll(b & below);
+    if (lane == 0) s_cnt[wave][k] = (uint32_t)__popcll(b);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    total[k] = 0;
+#pragma unroll
+    for (int w = 0; w < DN_WAVES; w++) {
+      if (w < wave) rank[k] += s_cnt[w][k];
+      total[k] += s_cnt[w][k];
+    }
+  }
+}
+
+// What both rules' plans measure of a source row (the flag bits they derive from it differ): the statistic g, the largest
+// activated scale of the row and of its split samples, the activated opacity.
+struct RowMeasures {
+  float g, max_scale, op, max_sample;
+  bool small, faint;
+};
+static __device__ __forceinline__ RowMeasures dn_row_measures(const float* __restrict__ scaling, const float* __restrict__ opacity,
+                                                              const float* __restrict__ accum, const float* __restrict__ denom,
+                                                              size_t i, float scale_bound, float min_opacity, float sample_div) {
+  RowMeasures m;
+  m.g = accum[i] / denom[i];   // (correctly rounded, as torch's)
+  if (m.g != m.g) m.g = 0.0f;  // grads[grads.isnan()] = 0
+  const float e0 = expf(scaling[3 * i]), e1 = expf(scaling[3 * i + 1]), e2 = expf(scaling[3 * i + 2]);
+  m.max_scale = fmaxf(fmaxf(e0, e1), e2);
+  m.small = m.max_scale <= scale_bound;
+  m.op = 1.0f / (1.0f + expf(-opacity[i]));
+  m.faint = m.op < min_opacity;
+  // the chain the host evaluates on the new rows: exp(log(exp(s) / (0.8 N)))
+  const float m0 = expf(logf(e0 / sample_div)), m1 = expf(logf(e1 / sample_div)), m2 = expf(logf(e2 / sample_div));
+  m.max_sample = fmaxf(fmaxf(m0, m1), m2);
+  return m;
+}
+
+// build_rotation (general_utils.py:78-99) of the normalised quaternion, row-major
+static __device__ __forceinline__ void dn_rotation(const float* __restrict__ q, float* R) {
+  const float r0 = q[0], r1 = q[1], r2 = q[2], r3 = q[3];
+  const float nrm = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
+  const float w = r0 / nrm, x = r1 / nrm, y = r2 / nrm, z = r3 / nrm;
+  R[0] = 1.0f - 2.0f * (y * y + z * z); R[1] = 2.0f * (x * y - w * z); R[2] = 2.0f * (x * z + w * y);
+  R[3] = 2.0f * (x * y + w * z); R[4] = 1.0f - 2.0f * (x * x + z * z); R[5] = 2.0f * (y * z - w * x);
+  R[6] = 2.0f * (x * z - w * y); R[7] = 2.0f * (y * z + w * x); R[8] = 1.0f - 2.0f * (x * x + y * y);
+}
+// samples = noise * exp(scaling); R samples + xyz
+static __device__ __forceinline__ void dn_sample_centre(const float* R, const float* s, const float* __restrict__ nz, const float* x,
+                                                        float* out) {
+  const float v0 = nz[0] * s[0], v1 = nz[1] * s[1], v2 = nz[2] * s[2];
+  out[0] = (R[0] * v0 + R[1] * v1 + R[2] * v2) + x[0];
+  out[1] = (R[3] * v0 + R[4] * v1 + R[5] * v2) + x[1];
+  out[2] = (R[6] * v0 + R[7] * v1 + R[8] * v2) + x[2];
+}
+// output row j (if it is one of the n_out rows): its table entry - source row and kind - and its centre
+static __device__ __forceinline__ void dn_put_row(uint32_t* __restrict__ table, float* __restrict__ xyz_out, uint32_t j, uint32_t n_out,
+                                                  size_t src, uint32_t kind, const float* x) {
+  if (j >= n_out) return;
+  table[j] = (uint32_t)src | (kind << DN_KIND_SHIFT);
+  xyz_out[3 * (size_t)j] = x[0]; xyz_out[3 * (size_t)j + 1] = x[1]; xyz_out[3 * (size_t)j + 2] = x[2];
+}
+// the N samples of split row i, the r-th of n_split split rows (the row of the host's noise.repeat(N, 1) order): sample k is
+// output row j0 + k stride
+static __device__ __forceinline__ void dn_put_samples(const float* __restrict__ scaling, const float* __restrict__ rotation,
+                                                      const float* __restrict__ noise, size_t i, const float* x, uint32_t r,
+                                                      uint32_t n_split, int N, uint32_t j0, uint32_t stride, uint32_t n_out,
+                                                      uint32_t* __restrict__ table, float* __restrict__ xyz_out) {
+  if (r >= n_split) return;
+  float R[9], c[3];
+  dn_rotation(rotation + 4 * i, R);
+  const float s[3] = {expf(scaling[3 * i]), expf(scaling[3 * i + 1]), expf(scaling[3 * i + 2])};
+  for (int k = 0; k < N; k++) {
+    dn_sample_centre(R, s, noise + 3 * ((size_t)k * n_split + r), x, c);
+    dn_put_row(table, xyz_out, j0 + (uint32_t)k * stride, n_out, i, GS_DENSIFY_SAMPLE, c);
+  }
+}
+
 // what a source row contributes, from its flag byte: [0] a survivor, [1] a clone, [2] it is split, [3] its samples are kept
 static __device__ __forceinline__ void dn_preds(unsigned f, bool in, bool* c) {
   const bool split = (f & GS_DENSIFY_SPLIT) != 0;
@@ -79,40 +173,21 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_plan_kernel(const float* __r
   const bool in = i < (size_t)P;
   unsigned f = 0;
   if (in) {
-    float g = accum[i] / denom[i];   // (correctly rounded, as torch's)
-    if (g != g) g = 0.0f;            // grads[grads.isnan()] = 0
-    const float e0 = expf(scaling[3 * i]), e1 = expf(scaling[3 * i + 1]), e2 = expf(scaling[3 * i + 2]);
-    const float max_scale = fmaxf(fmaxf(e0, e1), e2);
-    const bool small = max_scale <= scale_bound;
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
-    const bool faint = op < min_opacity;
-    // the chain the host evaluates on the new rows: exp(log(exp(s) / (0.8 N)))
-    const float m0 = expf(logf(e0 / sample_div)), m1 = expf(logf(e1 / sample_div)), m2 = expf(logf(e2 / sample_div));
-    const float max_sample = fmaxf(fmaxf(m0, m1), m2);
+    const RowMeasures m = dn_row_measures(scaling, opacity, accum, denom, i, scale_bound, min_opacity, sample_div);
     // DNGaussian's rule (gs_densify_plan_gated): clone and split also need get_opacity > opa_thresh; a NaN opacity selects nothing
-    const bool open = !gated || op > gate_opacity;
-    if (fabsf(g) >= max_grad && small && open) f |= GS_DENSIFY_CLONE;
-    if (g >= max_grad && !small && open) f |= GS_DENSIFY_SPLIT;
-    if (faint || (size_test && max_scale > world_bound)) f |= GS_DENSIFY_PRUNE_SELF;
-    if (faint || (size_test && max_sample > world_bound)) f |= GS_DENSIFY_PRUNE_SAMPLE;
+    const bool open = !gated || m.op > gate_opacity;
+    if (fabsf(m.g) >= max_grad && m.small && open) f |= GS_DENSIFY_CLONE;
+    if (m.g >= max_grad && !m.small && open) f |= GS_DENSIFY_SPLIT;
+    if (m.faint || (size_test && m.max_scale > world_bound)) f |= GS_DENSIFY_PRUNE_SELF;
+    if (m.faint || (size_test && m.max_sample > world_bound)) f |= GS_DENSIFY_PRUNE_SAMPLE;
     flags[i] = (uint8_t)f;
   }
   bool c[DN_NC];
   dn_preds(f, in, c);
   c[4] = in && (f & GS_DENSIFY_CLONE);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < DN_NC; k++) {
-    const unsigned long long b = __ballot(c[k]);
-    if (lane == 0) s_cnt[wave][k] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x < DN_NC) {
-    uint32_t s = 0;
-#pragma unroll
-    for (int w = 0; w < DN_WAVES; w++) s += s_cnt[w][threadIdx.x];
-    counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = s;
-  }
+  uint32_t rank[DN_NC], total[DN_NC];
+  dn_block_ranks<DN_NC>(c, s_cnt, rank, total);
+  if (threadIdx.x < DN_NC) counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = total[threadIdx.x];
 }
 
 // one workgroup: thread t owns the blocks [t per, (t + 1) per); exclusive prefixes in block order, totals last
@@ -158,66 +233,26 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_emit_kernel(const uint8_t* _
                                                                const float* __restrict__ scaling, const float* __restrict__ rotation,
                                                                const float* __restrict__ noise, int P, int N, EmitCounts n, uint32_t P2,
                                                                uint32_t* __restrict__ table, float* __restrict__ new_xyz) {
-  __shared__ uint32_t s_cnt[DN_WAVES][4];
-  // the counts the host sized the outputs with must be the plan's: anything else would place rows out of range
+  __shared__ uint32_t s_cnt[DN_WAVES][DN_NC];
+  // the counts the host sized the outputs with must be the plan's: anything else would place rows out of range (uniform over
+  // the grid: nobody reaches the barrier)
   if (totals[0] != n.n_keep || totals[1] != n.n_clone_keep || totals[2] != n.n_split || totals[3] != n.n_split_keep) return;
   const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
   const bool in = i < (size_t)P;
   const unsigned f = in ? flags[i] : 0u;
   bool c[4];
   dn_preds(f, in, c);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-  uint32_t rank[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const unsigned long long b = __ballot(c[k]);
-    rank[k] = (uint32_t)__popcll(b & below);
-    if (lane == 0) s_cnt[wave][k] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    for (int w = 0; w < wave; w++) rank[k] += s_cnt[w][k];
-    rank[k] += prefix[(size_t)blockIdx.x * DN_NC + k];   // ascending source row inside every group
-  }
+  uint32_t rank[4], total[4];
+  dn_block_ranks<4>(c, s_cnt, rank, total);
   if (!in) return;
-  const float x0 = xyz[3 * i], x1 = xyz[3 * i + 1], x2 = xyz[3 * i + 2];
-  if (c[0]) {
-    const uint32_t j = rank[0];
-    if (j < P2) {
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SURVIVOR << DN_KIND_SHIFT);
-      new_xyz[3 * (size_t)j] = x0; new_xyz[3 * (size_t)j + 1] = x1; new_xyz[3 * (size_t)j + 2] = x2;
-    }
-  }
-  if (c[1]) {
-    const uint32_t j = n.n_keep + rank[1];
-    if (j < P2) {
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_CLONED << DN_KIND_SHIFT);
-      new_xyz[3 * (size_t)j] = x0; new_xyz[3 * (size_t)j + 1] = x1; new_xyz[3 * (size_t)j + 2] = x2;
-    }
-  }
-  if (c[3]) {
-    // build_rotation (general_utils.py:78-99) of the normalised quaternion; samples = noise * exp(scaling); R samples + xyz
-    const float r0 = rotation[4 * i], r1 = rotation[4 * i + 1], r2 = rotation[4 * i + 2], r3 = rotation[4 * i + 3];
-    const float nrm = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
-    const float w = r0 / nrm, x = r1 / nrm, y = r2 / nrm, z = r3 / nrm;
-    const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - w * z), R02 = 2.0f * (x * z + w * y);
-    const float R10 = 2.0f * (x * y + w * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - w * x);
-    const float R20 = 2.0f * (x * z - w * y), R21 = 2.0f * (y * z + w * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-    const float s0 = expf(scaling[3 * i]), s1 = expf(scaling[3 * i + 1]), s2 = expf(scaling[3 * i + 2]);
-    const uint32_t r = rank[2];   // among ALL split rows: the row of the host's noise.repeat(N, 1) order
-    for (int k = 0; k < N; k++) {
-      const uint32_t j = n.n_keep + n.n_clone_keep + (uint32_t)k * n.n_split_keep + rank[3];
-      if (r >= n.n_split || j >= P2) continue;
-      const float* nz = noise + 3 * ((size_t)k * n.n_split + r);
-      const float v0 = nz[0] * s0, v1 = nz[1] * s1, v2 = nz[2] * s2;
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SAMPLE << DN_KIND_SHIFT);
-      new_xyz[3 * (size_t)j] = (R00 * v0 + R01 * v1 + R02 * v2) + x0;
-      new_xyz[3 * (size_t)j + 1] = (R10 * v0 + R11 * v1 + R12 * v2) + x1;
-      new_xyz[3 * (size_t)j + 2] = (R20 * v0 + R21 * v1 + R22 * v2) + x2;
-    }
-  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) rank[k] += prefix[(size_t)blockIdx.x * DN_NC + k];   // ascending source row inside every group
+  const float x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  if (c[0]) dn_put_row(table, new_xyz, rank[0], P2, i, GS_DENSIFY_SURVIVOR, x);
+  if (c[1]) dn_put_row(table, new_xyz, n.n_keep + rank[1], P2, i, GS_DENSIFY_CLONED, x);
+  if (c[3])   // rank[2]: among ALL split rows, kept or not
+    dn_put_samples(scaling, rotation, noise, i, x, rank[2], n.n_split, N, n.n_keep + n.n_clone_keep + rank[3], n.n_split_keep, P2,
+                   table, new_xyz);
 }
 
 // synthetic.morton_order's arithmetic in float64: q = clamp(rint((x - lo) / max(hi - lo, 1e-30) * 1023), 0, 1023), bits of
@@ -242,23 +277,27 @@ __global__ void __launch_bounds__(DN_BLOCK) morton_codes_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// The gather.  The flat buffers are field-major ([P, w_f] blocks back to back); workgroup (x, y) writes the 256 w_f floats of
-// rows [256 x, 256 x + 256) of field y: consecutive lanes write consecutive floats (fully coalesced), and read runs of one row
-// of the field.  The rows' table entries are fetched once per workgroup into LDS.
+// The gather, of both rules.  The flat buffers are field-major ([P, w_f] blocks back to back); workgroup (x, y) writes the
+// 256 w_f floats of rows [256 x, 256 x + 256) of field y: consecutive lanes write consecutive floats (fully coalesced), and read
+// runs of one row of the field.  The rows' table entries are fetched once per workgroup into LDS.
+// PROX (FSGS): the table may hold proximity rows - the neighbour's raw scaling (sample-transformed if the neighbour, whose kind
+// is in nb_kind, is a sample) and raw opacity, rotation (1, 0, 0, 0), every other field 0, moments +0.  Without PROX such an
+// entry is dropped, and there is no neighbour-kind array.
 // ------------------------------------------------------------------------------------------------------------------
 #define DN_MAX_FIELDS 8
 #define DN_UNROLL 4
+enum { DN_ROLE_COPY = 0, DN_ROLE_XYZ, DN_ROLE_SCALING, DN_ROLE_OPACITY, DN_ROLE_ROTATION };
 struct GatherFields {
   int n;
   int width[DN_MAX_FIELDS];
+  int role[DN_MAX_FIELDS];
   long long old_off[DN_MAX_FIELDS];  // start of the field's [P, w] block in the old buffers
   long long new_off[DN_MAX_FIELDS];  // ... of its [P2, w] block in the new ones
-  int xyz_field, scaling_field;
 };
 
-template <int WC>
-static __device__ __forceinline__ void gather_rows(const uint32_t* s_ent, const uint32_t* s_e, int rows, int w_rt, bool is_xyz,
-                                                   bool is_scaling, float sample_div, const float* __restrict__ new_xyz,
+template <int WC, bool PROX>
+static __device__ __forceinline__ void gather_rows(const uint32_t* s_ent, const uint32_t* s_e, const uint8_t* s_nk, int rows, int w_rt,
+                                                   int role, float sample_div, const float* __restrict__ new_xyz,
                                                    const float* __restrict__ op, const float* __restrict__ om,
                                                    const float* __restrict__ ov, float* __restrict__ np, float* __restrict__ nm,
                                                    float* __restrict__ nv) {
@@ -280,11 +319,16 @@ static __device__ __forceinline__ void gather_rows(const uint32_t* s_ent, const 
       ok[u] = true;
       const uint32_t kind = ent >> DN_KIND_SHIFT;
       const size_t so = (size_t)(ent & DN_ROW_MASK) * w + c;
-      if (is_xyz) {
+      const bool prox = PROX && kind == GS_DENSIFY_PROXIMITY;
+      if (role == DN_ROLE_XYZ) {
         p[u] = new_xyz[3 * (size_t)s_e[jl] + c];   // (a copy of the source's for a survivor or a clone)
-      } else {
+      } else if (role == DN_ROLE_SCALING) {
         p[u] = op[so];
-        if (is_scaling && kind == GS_DENSIFY_SAMPLE) p[u] = logf(expf(p[u]) / sample_div);
+        if (kind == GS_DENSIFY_SAMPLE || (prox && s_nk[jl] == GS_DENSIFY_SAMPLE)) p[u] = logf(expf(p[u]) / sample_div);
+      } else if (!prox || role == DN_ROLE_OPACITY) {   // a copy: every field of the other kinds, the opacity of a proximity row
+        p[u] = op[so];
+      } else if (role == DN_ROLE_ROTATION) {
+        p[u] = c == 0 ? 1.0f : 0.0f;
       }
       if (kind == GS_DENSIFY_SURVIVOR) {
         m[u] = om[so];
@@ -302,28 +346,32 @@ static __device__ __forceinline__ void gather_rows(const uint32_t* s_ent, const 
   }
 }
 
-__global__ void __launch_bounds__(DN_BLOCK) densify_gather_kernel(const long long* __restrict__ perm, const uint32_t* __restrict__ table,
-                                                                 const float* __restrict__ new_xyz, uint32_t P2,
-                                                                 const float* __restrict__ old_p, const float* __restrict__ old_m,
-                                                                 const float* __restrict__ old_v, uint32_t P, float* __restrict__ new_p,
-                                                                 float* __restrict__ new_m, float* __restrict__ new_v, GatherFields f,
-                                                                 float sample_div) {
-  __shared__ uint32_t s_ent[DN_BLOCK], s_e[DN_BLOCK];
+// one workgroup of the gather; s_ent, s_e (and s_nk with PROX): DN_BLOCK entries of LDS each
+template <bool PROX>
+static __device__ __forceinline__ void gather_block(uint32_t* s_ent, uint32_t* s_e, uint8_t* s_nk, const long long* __restrict__ perm,
+                                                    const uint32_t* __restrict__ table, const uint8_t* __restrict__ nb_kind,
+                                                    const float* __restrict__ new_xyz, uint32_t P2, const float* __restrict__ old_p,
+                                                    const float* __restrict__ old_m, const float* __restrict__ old_v, uint32_t P,
+                                                    float* __restrict__ new_p, float* __restrict__ new_m, float* __restrict__ new_v,
+                                                    const GatherFields& f, float sample_div) {
   const int fi = blockIdx.y;
   const uint32_t j0 = blockIdx.x * DN_BLOCK;
   const int rows = (int)min((uint32_t)DN_BLOCK, P2 - j0);
   {
     uint32_t ent = DN_INVALID, e = 0;
+    uint8_t nk = 0;
     if ((int)threadIdx.x < rows) {
       const unsigned long long ee = perm ? (unsigned long long)perm[j0 + threadIdx.x] : (unsigned long long)(j0 + threadIdx.x);
       if (ee < P2) {
         e = (uint32_t)ee;
         ent = table[e];
-        if ((ent >> DN_KIND_SHIFT) > GS_DENSIFY_SAMPLE || (ent & DN_ROW_MASK) >= P) ent = DN_INVALID;
+        if (PROX) nk = nb_kind[e];
+        if ((!PROX && (ent >> DN_KIND_SHIFT) > GS_DENSIFY_SAMPLE) || (ent & DN_ROW_MASK) >= P) ent = DN_INVALID;
       }
     }
     s_ent[threadIdx.x] = ent;
     s_e[threadIdx.x] = e;
+    if (PROX) s_nk[threadIdx.x] = nk;
   }
   __syncthreads();
   const int w = f.width[fi];
@@ -334,8 +382,7 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_gather_kernel(const long lon
   float* np = new_p + base;
   float* nm = new_m + base;
   float* nv = new_v + base;
-  const bool is_xyz = fi == f.xyz_field, is_scaling = fi == f.scaling_field;
-#define DN_GATHER(WC) gather_rows<WC>(s_ent, s_e, rows, w, is_xyz, is_scaling, sample_div, new_xyz, op, om, ov, np, nm, nv)
+#define DN_GATHER(WC) gather_rows<WC, PROX>(s_ent, s_e, s_nk, rows, w, f.role[fi], sample_div, new_xyz, op, om, ov, np, nm, nv)
   switch (w) {   // (workgroup-uniform: the division by the row width is by a constant for the model's own widths)
     case 1: DN_GATHER(1); break;
     case 3: DN_GATHER(3); break;
@@ -344,6 +391,66 @@ __global__ void __launch_bounds__(DN_BLOCK) densify_gather_kernel(const long lon
     default: DN_GATHER(0); break;
   }
 #undef DN_GATHER
+}
+
+__global__ void __launch_bounds__(DN_BLOCK) densify_gather_kernel(const long long* __restrict__ perm, const uint32_t* __restrict__ table,
+                                                                 const float* __restrict__ new_xyz, uint32_t P2,
+                                                                 const float* __restrict__ old_p, const float* __restrict__ old_m,
+                                                                 const float* __restrict__ old_v, uint32_t P, float* __restrict__ new_p,
+                                                                 float* __restrict__ new_m, float* __restrict__ new_v, GatherFields f,
+                                                                 float sample_div) {
+  __shared__ uint32_t s_ent[DN_BLOCK], s_e[DN_BLOCK];
+  gather_block<false>(s_ent, s_e, nullptr, perm, table, nullptr, new_xyz, P2, old_p, old_m, old_v, P, new_p, new_m, new_v, f,
+                      sample_div);
+}
+
+__global__ void __launch_bounds__(DN_BLOCK) fsgs_gather_kernel(const long long* __restrict__ perm, const uint32_t* __restrict__ table,
+                                                              const uint8_t* __restrict__ nb_kind, const float* __restrict__ new_xyz,
+                                                              uint32_t P2, const float* __restrict__ old_p, const float* __restrict__ old_m,
+                                                              const float* __restrict__ old_v, uint32_t P, float* __restrict__ new_p,
+                                                              float* __restrict__ new_m, float* __restrict__ new_v, GatherFields f,
+                                                              float sample_div) {
+  __shared__ uint32_t s_ent[DN_BLOCK], s_e[DN_BLOCK];
+  __shared__ uint8_t s_nk[DN_BLOCK];
+  gather_block<true>(s_ent, s_e, s_nk, perm, table, nb_kind, new_xyz, P2, old_p, old_m, old_v, P, new_p, new_m, new_v, f, sample_div);
+}
+
+// Both gather entry points behind their null checks: the field table from the widths and the special fields - special[0] the
+// centres (width 3), [1] the scaling, with nb_kind also [2] the opacity and [3] the rotation; all distinct - and the launch.
+static int dn_gather(const int64_t* perm, const uint32_t* table, const uint8_t* nb_kind, const float* new_xyz, int32_t P2,
+                     const float* old_flat, const float* old_exp_avg, const float* old_exp_avg_sq, int32_t P, float* new_flat,
+                     float* new_exp_avg, float* new_exp_avg_sq, int32_t nfields, const int32_t* widths, const int32_t* special,
+                     float sample_div, void* stream) {
+  if (P < 1 || P > (int32_t)DN_ROW_MASK || P2 < 1 || P2 > (int32_t)DN_ROW_MASK || nfields < 1 || nfields > DN_MAX_FIELDS)
+    return GS_E_SHAPE;
+  GatherFields f;
+  f.n = nfields;
+  long long co = 0;
+  for (int q = 0; q < DN_MAX_FIELDS; q++) {
+    const int w = q < nfields ? widths[q] : 0;
+    if (q < nfields && (w < 1 || w > 4096)) return GS_E_SHAPE;
+    f.width[q] = w;
+    f.role[q] = DN_ROLE_COPY;
+    f.old_off[q] = co * P;
+    f.new_off[q] = co * P2;
+    co += w;
+  }
+  for (int a = 0; a < (nb_kind ? 4 : 2); a++) {
+    if (special[a] < 0 || special[a] >= nfields || f.role[special[a]] != DN_ROLE_COPY) return GS_E_SHAPE;
+    f.role[special[a]] = DN_ROLE_XYZ + a;
+  }
+  if (widths[special[0]] != 3) return GS_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  GS_PROF(ST_MODEL, s);
+  const dim3 grid((unsigned)dn_blocks((size_t)P2), (unsigned)nfields);
+  if (nb_kind)
+    hipLaunchKernelGGL(fsgs_gather_kernel, grid, dim3(DN_BLOCK), 0, s, (const long long*)perm, table, nb_kind, new_xyz, (uint32_t)P2,
+                       old_flat, old_exp_avg, old_exp_avg_sq, (uint32_t)P, new_flat, new_exp_avg, new_exp_avg_sq, f, sample_div);
+  else
+    hipLaunchKernelGGL(densify_gather_kernel, grid, dim3(DN_BLOCK), 0, s, (const long long*)perm, table, new_xyz, (uint32_t)P2, old_flat,
+                       old_exp_avg, old_exp_avg_sq, (uint32_t)P, new_flat, new_exp_avg, new_exp_avg_sq, f, sample_div);
+  GS_LAUNCH_CHECK(s, 0);
+  return GS_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -369,19 +476,12 @@ static inline PruneTmp pr_tmp_view(void* buf, size_t P) {
 }
 
 __global__ void __launch_bounds__(DN_BLOCK) prune_plan_kernel(const uint8_t* __restrict__ mask, int P, uint32_t* __restrict__ counts) {
-  __shared__ uint32_t s_cnt[DN_WAVES];
+  __shared__ uint32_t s_cnt[DN_WAVES][DN_NC];
   const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
-  const bool keep = i < (size_t)P && mask[i] == 0;
-  const unsigned long long b = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
-  __syncthreads();
-  if (threadIdx.x < DN_NC) {
-    uint32_t s = 0;
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int w = 0; w < DN_WAVES; w++) s += s_cnt[w];
-    counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = s;
-  }
+  const bool c[1] = {i < (size_t)P && mask[i] == 0};
+  uint32_t rank[1], total[1];
+  dn_block_ranks<1>(c, s_cnt, rank, total);
+  if (threadIdx.x < DN_NC) counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = threadIdx.x == 0 ? total[0] : 0u;
 }
 
 __global__ void __launch_bounds__(DN_BLOCK) prune_emit_kernel(const uint8_t* __restrict__ mask, const uint32_t* __restrict__ prefix,
@@ -391,22 +491,18 @@ __global__ void __launch_bounds__(DN_BLOCK) prune_emit_kernel(const uint8_t* __r
                                                              uint32_t* __restrict__ table, float* __restrict__ new_xyz,
                                                              float* __restrict__ new_accum, float* __restrict__ new_denom,
                                                              float* __restrict__ new_radii) {
-  __shared__ uint32_t s_cnt[DN_WAVES];
+  __shared__ uint32_t s_cnt[DN_WAVES][DN_NC];
   // the count the host sized the outputs with must be the plan's (uniform over the grid: nobody reaches the barrier)
   if (totals[0] != P2) return;
   const size_t i = (size_t)blockIdx.x * DN_BLOCK + threadIdx.x;
-  const bool keep = i < (size_t)P && mask[i] == 0;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned long long b = __ballot(keep);
-  uint32_t rank = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(b);
-  __syncthreads();
-  for (int w = 0; w < wave; w++) rank += s_cnt[w];
-  if (!keep) return;
-  const size_t j = (size_t)prefix[(size_t)blockIdx.x * DN_NC] + rank;   // ascending source row: the old relative order
+  const bool c[1] = {i < (size_t)P && mask[i] == 0};
+  uint32_t rank[1], total[1];
+  dn_block_ranks<1>(c, s_cnt, rank, total);
+  if (!c[0]) return;
+  const size_t j = (size_t)prefix[(size_t)blockIdx.x * DN_NC] + rank[0];   // ascending source row: the old relative order
   if (j >= (size_t)P2) return;
-  table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SURVIVOR << DN_KIND_SHIFT);
-  new_xyz[3 * j] = xyz[3 * i]; new_xyz[3 * j + 1] = xyz[3 * i + 1]; new_xyz[3 * j + 2] = xyz[3 * i + 2];
+  const float x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  dn_put_row(table, new_xyz, (uint32_t)j, P2, i, GS_DENSIFY_SURVIVOR, x);
   new_accum[j] = accum[i];
   new_denom[j] = denom[i];
   new_radii[j] = radii[i];
@@ -486,30 +582,9 @@ int gs_densify_gather(const int64_t* perm, const uint32_t* table, const float* n
                       float sample_div, void* stream) {
   if (!table || !new_xyz || !old_flat || !old_exp_avg || !old_exp_avg_sq || !new_flat || !new_exp_avg || !new_exp_avg_sq || !widths)
     return GS_E_NULL;
-  if (P < 1 || P > (int32_t)DN_ROW_MASK || P2 < 1 || P2 > (int32_t)DN_ROW_MASK || nfields < 1 || nfields > DN_MAX_FIELDS ||
-      xyz_field < 0 || xyz_field >= nfields || scaling_field < 0 || scaling_field >= nfields || xyz_field == scaling_field)
-    return GS_E_SHAPE;
-  GatherFields f;
-  f.n = nfields;
-  f.xyz_field = xyz_field;
-  f.scaling_field = scaling_field;
-  long long co = 0;
-  for (int q = 0; q < DN_MAX_FIELDS; q++) {
-    const int w = q < nfields ? widths[q] : 0;
-    if (q < nfields && (w < 1 || w > 4096)) return GS_E_SHAPE;
-    f.width[q] = w;
-    f.old_off[q] = co * P;
-    f.new_off[q] = co * P2;
-    co += w;
-  }
-  if (widths[xyz_field] != 3) return GS_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  GS_PROF(ST_MODEL, s);
-  hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)dn_blocks((size_t)P2), (unsigned)nfields), dim3(DN_BLOCK), 0, s,
-                     (const long long*)perm, table, new_xyz, (uint32_t)P2, old_flat, old_exp_avg, old_exp_avg_sq, (uint32_t)P, new_flat,
-                     new_exp_avg, new_exp_avg_sq, f, sample_div);
-  GS_LAUNCH_CHECK(s, 0);
-  return GS_OK;
+  const int32_t special[2] = {xyz_field, scaling_field};
+  return dn_gather(perm, table, nullptr, new_xyz, P2, old_flat, old_exp_avg, old_exp_avg_sq, P, new_flat, new_exp_avg, new_exp_avg_sq,
+                   nfields, widths, special, sample_div, stream);
 }
 
 size_t gs_prune_tmp_bytes(int32_t P) { return P < 1 ? 0 : pr_tmp_bytes((size_t)P); }
@@ -595,30 +670,6 @@ static inline FsgsTmp fs_tmp_view(void* buf, size_t P) {
   return t;
 }
 
-// In-block exclusive ranks of K predicates - ballot / popcount inside the wave, the waves' counts through LDS - and the block's
-// counts.  Every thread of the workgroup calls it (it synchronises).
-template <int K>
-static __device__ __forceinline__ void fs_block_ranks(const bool* c, uint32_t (*s_cnt)[DN_NC], uint32_t* rank, uint32_t* total) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    const unsigned long long b = __ballot(c[k]);
-    rank[k] = (uint32_t)__popcll(b & below);
-    if (lane == 0) s_cnt[wave][k] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    total[k] = 0;
-#pragma unroll
-    for (int w = 0; w < DN_WAVES; w++) {
-      if (w < wave) rank[k] += s_cnt[w][k];
-      total[k] += s_cnt[w][k];
-    }
-  }
-}
-
 static __device__ __forceinline__ bool fs_pruned(unsigned f, uint32_t kind, int prune_on) {
   return prune_on && (f & (kind == GS_DENSIFY_SAMPLE ? GS_DENSIFY_FSGS_PRUNE_SAMPLE : GS_DENSIFY_FSGS_PRUNE_SELF)) != 0;
 }
@@ -636,26 +687,18 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_plan_kernel(const float* __rest
   const bool in = i < (size_t)P;
   unsigned f = 0;
   if (in) {
-    float g = accum[i] / denom[i];
-    if (g != g) g = 0.0f;
-    const float e0 = expf(scaling[3 * i]), e1 = expf(scaling[3 * i + 1]), e2 = expf(scaling[3 * i + 2]);
-    const float max_scale = fmaxf(fmaxf(e0, e1), e2);
-    const bool small = max_scale <= scale_bound;
-    const float op = 1.0f / (1.0f + expf(-opacity[i]));
-    const bool faint = op < min_opacity;
-    const float m0 = expf(logf(e0 / sample_div)), m1 = expf(logf(e1 / sample_div)), m2 = expf(logf(e2 / sample_div));
-    const float max_sample = fmaxf(fmaxf(m0, m1), m2);
-    if (fabsf(g) >= max_grad && small) f |= GS_DENSIFY_FSGS_CLONE;
-    if (g >= max_grad && max_scale > scale_bound) f |= GS_DENSIFY_FSGS_GRAD_SPLIT;
-    if (faint || (size_test && max_scale > world_bound)) f |= GS_DENSIFY_FSGS_PRUNE_SELF;
-    if (faint || (size_test && max_sample > world_bound)) f |= GS_DENSIFY_FSGS_PRUNE_SAMPLE;
-    if (max_scale > extent_bound) f |= GS_DENSIFY_FSGS_WIDE_SELF;
-    if (max_sample > extent_bound) f |= GS_DENSIFY_FSGS_WIDE_SAMPLE;
+    const RowMeasures m = dn_row_measures(scaling, opacity, accum, denom, i, scale_bound, min_opacity, sample_div);
+    if (fabsf(m.g) >= max_grad && m.small) f |= GS_DENSIFY_FSGS_CLONE;
+    if (m.g >= max_grad && m.max_scale > scale_bound) f |= GS_DENSIFY_FSGS_GRAD_SPLIT;
+    if (m.faint || (size_test && m.max_scale > world_bound)) f |= GS_DENSIFY_FSGS_PRUNE_SELF;
+    if (m.faint || (size_test && m.max_sample > world_bound)) f |= GS_DENSIFY_FSGS_PRUNE_SAMPLE;
+    if (m.max_scale > extent_bound) f |= GS_DENSIFY_FSGS_WIDE_SELF;
+    if (m.max_sample > extent_bound) f |= GS_DENSIFY_FSGS_WIDE_SAMPLE;
     flags[i] = (uint8_t)f;
   }
   const bool c[1] = {in && (f & GS_DENSIFY_FSGS_CLONE)};
   uint32_t rank[1], total[1];
-  fs_block_ranks<1>(c, s_cnt, rank, total);
+  dn_block_ranks<1>(c, s_cnt, rank, total);
   if (threadIdx.x < DN_NC) counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = threadIdx.x == 0 ? total[0] : 0u;
 }
 
@@ -667,7 +710,7 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_centres_kernel(const uint8_t* _
   const bool in = i < (size_t)P;
   const bool c[1] = {in && (flags[i] & GS_DENSIFY_FSGS_CLONE)};
   uint32_t rank[1], total[1];
-  fs_block_ranks<1>(c, s_cnt, rank, total);
+  dn_block_ranks<1>(c, s_cnt, rank, total);
   if (!in) return;
   const float x0 = xyz[3 * i], x1 = xyz[3 * i + 1], x2 = xyz[3 * i + 2];
   xyz1[3 * i] = x0; xyz1[3 * i + 1] = x1; xyz1[3 * i + 2] = x2;
@@ -704,7 +747,7 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_merge_kernel(uint8_t* __restric
   bool c[DN_NC];
   fs_merge_preds(f, in, prune_on, c);
   uint32_t rank[DN_NC], total[DN_NC];
-  fs_block_ranks<DN_NC>(c, s_cnt, rank, total);
+  dn_block_ranks<DN_NC>(c, s_cnt, rank, total);
   if (threadIdx.x < DN_NC) counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = total[threadIdx.x];
 }
 
@@ -728,47 +771,16 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_emit_kernel(const uint8_t* __re
   fs_merge_preds(f, in, prune_on, m);
   const bool c[3] = {m[1], in && (f & GS_DENSIFY_FSGS_CLONE), m[0]};   // stays, cloned, split
   uint32_t rank[3], total[3];
-  fs_block_ranks<3>(c, s_cnt, rank, total);
+  dn_block_ranks<3>(c, s_cnt, rank, total);
   if (!in) return;
   rank[0] += prefix_b[(size_t)blockIdx.x * DN_NC + 1];
   rank[1] += prefix_a[(size_t)blockIdx.x * DN_NC];
   rank[2] += prefix_b[(size_t)blockIdx.x * DN_NC];
-  const float x0 = xyz[3 * i], x1 = xyz[3 * i + 1], x2 = xyz[3 * i + 2];
-  if (c[0]) {
-    const uint32_t j = rank[0];
-    if (j < nQ) {
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SURVIVOR << DN_KIND_SHIFT);
-      xyz_q[3 * (size_t)j] = x0; xyz_q[3 * (size_t)j + 1] = x1; xyz_q[3 * (size_t)j + 2] = x2;
-    }
-  }
-  if (c[1]) {
-    const uint32_t j = n.n_stay + rank[1];
-    if (j < nQ) {
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_CLONED << DN_KIND_SHIFT);
-      xyz_q[3 * (size_t)j] = x0; xyz_q[3 * (size_t)j + 1] = x1; xyz_q[3 * (size_t)j + 2] = x2;
-    }
-  }
-  if (c[2]) {
-    // as densify_emit_kernel: build_rotation of the normalised quaternion; samples = noise * exp(scaling); R samples + xyz
-    const float r0 = rotation[4 * i], r1 = rotation[4 * i + 1], r2 = rotation[4 * i + 2], r3 = rotation[4 * i + 3];
-    const float nrm = sqrtf(r0 * r0 + r1 * r1 + r2 * r2 + r3 * r3);
-    const float w = r0 / nrm, x = r1 / nrm, y = r2 / nrm, z = r3 / nrm;
-    const float R00 = 1.0f - 2.0f * (y * y + z * z), R01 = 2.0f * (x * y - w * z), R02 = 2.0f * (x * z + w * y);
-    const float R10 = 2.0f * (x * y + w * z), R11 = 1.0f - 2.0f * (x * x + z * z), R12 = 2.0f * (y * z - w * x);
-    const float R20 = 2.0f * (x * z - w * y), R21 = 2.0f * (y * z + w * x), R22 = 1.0f - 2.0f * (x * x + y * y);
-    const float s0 = expf(scaling[3 * i]), s1 = expf(scaling[3 * i + 1]), s2 = expf(scaling[3 * i + 2]);
-    const uint32_t r = rank[2];
-    for (int k = 0; k < N; k++) {
-      const uint32_t j = n.n_stay + n.n_clone + (uint32_t)k * n.n_split + r;
-      if (r >= n.n_split || j >= nQ) continue;
-      const float* nz = noise + 3 * ((size_t)k * n.n_split + r);
-      const float v0 = nz[0] * s0, v1 = nz[1] * s1, v2 = nz[2] * s2;
-      table[j] = (uint32_t)i | ((uint32_t)GS_DENSIFY_SAMPLE << DN_KIND_SHIFT);
-      xyz_q[3 * (size_t)j] = (R00 * v0 + R01 * v1 + R02 * v2) + x0;
-      xyz_q[3 * (size_t)j + 1] = (R10 * v0 + R11 * v1 + R12 * v2) + x1;
-      xyz_q[3 * (size_t)j + 2] = (R20 * v0 + R21 * v1 + R22 * v2) + x2;
-    }
-  }
+  const float x[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  if (c[0]) dn_put_row(table, xyz_q, rank[0], nQ, i, GS_DENSIFY_SURVIVOR, x);
+  if (c[1]) dn_put_row(table, xyz_q, n.n_stay + rank[1], nQ, i, GS_DENSIFY_CLONED, x);
+  if (c[2])
+    dn_put_samples(scaling, rotation, noise, i, x, rank[2], n.n_split, N, n.n_stay + n.n_clone + rank[2], n.n_split, nQ, table, xyz_q);
 }
 
 #define FS_Q_KEEP 1u
@@ -806,7 +818,7 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_prox_plan_kernel(const uint8_t*
                           ((unsigned)c[3] << (FS_Q_CHILD_SHIFT + 1)) | ((unsigned)c[4] << (FS_Q_CHILD_SHIFT + 2)));
   }
   uint32_t rank[DN_NC], total[DN_NC];
-  fs_block_ranks<DN_NC>(c, s_cnt, rank, total);
+  dn_block_ranks<DN_NC>(c, s_cnt, rank, total);
   if (threadIdx.x < DN_NC) counts[(size_t)blockIdx.x * DN_NC + threadIdx.x] = total[threadIdx.x];
 }
 
@@ -834,7 +846,7 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_final_rows_kernel(const uint8_t
   const bool c[DN_NC] = {(q & FS_Q_KEEP) != 0, (q & FS_Q_SEL) != 0, ((q >> FS_Q_CHILD_SHIFT) & 1u) != 0,
                          ((q >> (FS_Q_CHILD_SHIFT + 1)) & 1u) != 0, ((q >> (FS_Q_CHILD_SHIFT + 2)) & 1u) != 0};
   uint32_t rank[DN_NC], total[DN_NC];
-  fs_block_ranks<DN_NC>(c, s_cnt, rank, total);
+  dn_block_ranks<DN_NC>(c, s_cnt, rank, total);
   if (!in) return;
 #pragma unroll
   for (int k = 0; k < DN_NC; k++) rank[k] += prefix[(size_t)blockIdx.x * DN_NC + k];
@@ -874,112 +886,6 @@ __global__ void __launch_bounds__(DN_BLOCK) fsgs_final_prox_kernel(const uint8_t
   nb_kind[o] = (uint8_t)(e2 >> DN_KIND_SHIFT);
 #pragma unroll
   for (int a = 0; a < 3; a++) new_xyz[3 * o + a] = (xyz_q[3 * (size_t)partner + a] + xyz_q[3 * (size_t)nb + a]) / 2.0f;
-}
-
-// ---- the gather, with the proximity rows: the neighbour's raw scaling (sample-transformed if the neighbour is a sample) and raw
-// opacity, rotation (1, 0, 0, 0), every other field 0, moments +0
-struct FsgsGatherFields {
-  GatherFields g;
-  int opacity_field, rotation_field;
-};
-
-template <int WC>
-static __device__ __forceinline__ void fsgs_gather_rows(const uint32_t* s_ent, const uint32_t* s_e, const uint8_t* s_nk, int rows, int w_rt,
-                                                        int role, float sample_div, const float* __restrict__ new_xyz,
-                                                        const float* __restrict__ op, const float* __restrict__ om,
-                                                        const float* __restrict__ ov, float* __restrict__ np, float* __restrict__ nm,
-                                                        float* __restrict__ nv) {
-  const int w = WC ? WC : w_rt;
-  const int total = rows * w;
-  for (int base = threadIdx.x; base < total; base += DN_BLOCK * DN_UNROLL) {
-    float p[DN_UNROLL], m[DN_UNROLL], v[DN_UNROLL];
-    bool ok[DN_UNROLL];
-#pragma unroll
-    for (int u = 0; u < DN_UNROLL; u++) {
-      const int idx = base + u * DN_BLOCK;
-      p[u] = m[u] = v[u] = 0.0f;
-      ok[u] = false;
-      if (idx >= total) continue;
-      const int jl = idx / w, c = idx - jl * w;
-      const uint32_t ent = s_ent[jl];
-      if (ent == DN_INVALID) continue;
-      ok[u] = true;
-      const uint32_t kind = ent >> DN_KIND_SHIFT;
-      const size_t so = (size_t)(ent & DN_ROW_MASK) * w + c;
-      const bool prox = kind == GS_DENSIFY_PROXIMITY;
-      if (role == 1) {   // xyz
-        p[u] = new_xyz[3 * (size_t)s_e[jl] + c];
-      } else if (role == 2) {   // scaling
-        p[u] = op[so];
-        if (kind == GS_DENSIFY_SAMPLE || (prox && s_nk[jl] == GS_DENSIFY_SAMPLE)) p[u] = logf(expf(p[u]) / sample_div);
-      } else if (!prox || role == 3) {   // a copy: every field of the other kinds, the opacity of a proximity row
-        p[u] = op[so];
-      } else if (role == 4) {   // rotation of a proximity row
-        p[u] = c == 0 ? 1.0f : 0.0f;
-      }
-      if (kind == GS_DENSIFY_SURVIVOR) {
-        m[u] = om[so];
-        v[u] = ov[so];
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < DN_UNROLL; u++) {
-      const int idx = base + u * DN_BLOCK;
-      if (!ok[u]) continue;
-      np[idx] = p[u];
-      nm[idx] = m[u];
-      nv[idx] = v[u];
-    }
-  }
-}
-
-__global__ void __launch_bounds__(DN_BLOCK) fsgs_gather_kernel(const long long* __restrict__ perm, const uint32_t* __restrict__ table,
-                                                              const uint8_t* __restrict__ nb_kind, const float* __restrict__ new_xyz,
-                                                              uint32_t P2, const float* __restrict__ old_p, const float* __restrict__ old_m,
-                                                              const float* __restrict__ old_v, uint32_t P, float* __restrict__ new_p,
-                                                              float* __restrict__ new_m, float* __restrict__ new_v, FsgsGatherFields ff,
-                                                              float sample_div) {
-  __shared__ uint32_t s_ent[DN_BLOCK], s_e[DN_BLOCK];
-  __shared__ uint8_t s_nk[DN_BLOCK];
-  const GatherFields& f = ff.g;
-  const int fi = blockIdx.y;
-  const uint32_t j0 = blockIdx.x * DN_BLOCK;
-  const int rows = (int)min((uint32_t)DN_BLOCK, P2 - j0);
-  {
-    uint32_t ent = DN_INVALID, e = 0;
-    uint8_t nk = 0;
-    if ((int)threadIdx.x < rows) {
-      const unsigned long long ee = perm ? (unsigned long long)perm[j0 + threadIdx.x] : (unsigned long long)(j0 + threadIdx.x);
-      if (ee < P2) {
-        e = (uint32_t)ee;
-        ent = table[e];
-        nk = nb_kind[e];
-        if ((ent & DN_ROW_MASK) >= P) ent = DN_INVALID;
-      }
-    }
-    s_ent[threadIdx.x] = ent;
-    s_e[threadIdx.x] = e;
-    s_nk[threadIdx.x] = nk;
-  }
-  __syncthreads();
-  const int w = f.width[fi];
-  const float* op = old_p + f.old_off[fi];
-  const float* om = old_m + f.old_off[fi];
-  const float* ov = old_v + f.old_off[fi];
-  const size_t base = (size_t)f.new_off[fi] + (size_t)j0 * w;
-  float* np = new_p + base;
-  float* nm = new_m + base;
-  float* nv = new_v + base;
-  const int role = fi == f.xyz_field ? 1 : fi == f.scaling_field ? 2 : fi == ff.opacity_field ? 3 : fi == ff.rotation_field ? 4 : 0;
-#define FS_GATHER(WC) fsgs_gather_rows<WC>(s_ent, s_e, s_nk, rows, w, role, sample_div, new_xyz, op, om, ov, np, nm, nv)
-  switch (w) {
-    case 1: FS_GATHER(1); break;
-    case 3: FS_GATHER(3); break;
-    case 4: FS_GATHER(4); break;
-    case 48: FS_GATHER(48); break;
-    default: FS_GATHER(0); break;
-  }
-#undef FS_GATHER
 }
 
 extern "C" {
@@ -1090,37 +996,8 @@ int gs_densify_fsgs_gather(const int64_t* perm, const uint32_t* table, const uin
   if (!table || !nb_kind || !new_xyz || !old_flat || !old_exp_avg || !old_exp_avg_sq || !new_flat || !new_exp_avg || !new_exp_avg_sq ||
       !widths)
     return GS_E_NULL;
-  if (P < 1 || P > (int32_t)DN_ROW_MASK || P2 < 1 || P2 > (int32_t)DN_ROW_MASK || nfields < 1 || nfields > DN_MAX_FIELDS)
-    return GS_E_SHAPE;
   const int32_t special[4] = {xyz_field, scaling_field, opacity_field, rotation_field};
-  for (int a = 0; a < 4; a++) {
-    if (special[a] < 0 || special[a] >= nfields) return GS_E_SHAPE;
-    for (int b = 0; b < a; b++)
-      if (special[a] == special[b]) return GS_E_SHAPE;
-  }
-  FsgsGatherFields ff;
-  GatherFields& f = ff.g;
-  f.n = nfields;
-  f.xyz_field = xyz_field;
-  f.scaling_field = scaling_field;
-  ff.opacity_field = opacity_field;
-  ff.rotation_field = rotation_field;
-  long long co = 0;
-  for (int q = 0; q < DN_MAX_FIELDS; q++) {
-    const int w = q < nfields ? widths[q] : 0;
-    if (q < nfields && (w < 1 || w > 4096)) return GS_E_SHAPE;
-    f.width[q] = w;
-    f.old_off[q] = co * P;
-    f.new_off[q] = co * P2;
-    co += w;
-  }
-  if (widths[xyz_field] != 3) return GS_E_SHAPE;
-  hipStream_t s = (hipStream_t)stream;
-  GS_PROF(ST_MODEL, s);
-  hipLaunchKernelGGL(fsgs_gather_kernel, dim3((unsigned)dn_blocks((size_t)P2), (unsigned)nfields), dim3(DN_BLOCK), 0, s,
-                     (const long long*)perm, table, nb_kind, new_xyz, (uint32_t)P2, old_flat, old_exp_avg, old_exp_avg_sq, (uint32_t)P,
-                     new_flat, new_exp_avg, new_exp_avg_sq, ff, sample_div);
-  GS_LAUNCH_CHECK(s, 0);
-  return GS_OK;
+  return dn_gather(perm, table, nb_kind, new_xyz, P2, old_flat, old_exp_avg, old_exp_avg_sq, P, new_flat, new_exp_avg, new_exp_avg_sq,
+                   nfields, widths, special, sample_div, stream);
 }
 }

@@ -293,6 +293,23 @@ def _stream_of(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
 
 
+def _f32(v):
+    """A Python float as the kernels' thresholds take it: torch compares fp32 tensors with Python floats by rounding the scalar
+    to fp32 ONCE, so the products are formed in double as the host paths form them, then rounded."""
+    import ctypes as C
+    return C.c_float(v).value
+
+
+def _split_noise(ns, N, generator, device):
+    """The [N ns, 3] normal draws of ns split rows, None without any: ONE draw from `generator` (default: seed 0), on the CPU so
+    every rank and every backend sees the same numbers, then moved to `device`."""
+    if not ns:
+        return None
+    if generator is None:
+        generator = torch.Generator().manual_seed(0)
+    return torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(device)
+
+
 class _FusedActivations(torch.autograd.Function):
     """scales, rotations, opacities = exp(_scaling), normalize(_rotation), sigmoid(_opacity) in one kernel each way
     (gs_activations_fwd / gs_activations_bwd); the backward writes straight into the model's flat gradient buffer
@@ -615,14 +632,17 @@ class GaussianModelLite:
         state; copied values are the host path's bit for bit, the split samples' centres and scales agree to the last bits
         (tests/test_gpu_densify_device.py).  With `decisions`, or when every row is pruned, the host path runs."""
         if on_device:
-            api = getattr(self.optimizer, "api", None)
-            if not (self.flat.is_cuda and isinstance(self.optimizer, FlatAdam) and hasattr(api, "_densify_plan")):
-                raise RuntimeError("densify_and_prune(on_device=True) needs a GPU model built with the HIP api (flat Adam state); "
-                                   "there is no fallback")
+            self._require_device_form("densify_and_prune", "densify_plan")
             if decisions is None:
                 out = self._densify_on_device(max_grad, min_opacity, extent, max_screen_size, generator, N)
                 if out is not None:
                     return out
+        return self._clone_split_prune(max_grad, min_opacity, extent, bool(max_screen_size), None, generator, N, decisions)
+
+    def _clone_split_prune(self, max_grad, min_opacity, extent, world_size_prune, gate_opacity, generator, N, decisions=None):
+        """The host body of densify_and_prune and, with its two parameters, of densify_and_prune_dng: world_size_prune - the
+        final prune's max scale > 0.1 * extent term (DNGaussian has none); gate_opacity - not None: clone and split also need
+        sigmoid(opacity) > gate_opacity (DNGaussian's opa_thresh).  Returns (n_clone, n_split, n_pruned)."""
         with torch.no_grad():
             P0 = self.P
             grads = self.xyz_gradient_accum / self.denom
@@ -633,6 +653,9 @@ class GaussianModelLite:
             small = max_scale <= self.percent_dense * extent
             clone = (g.abs() >= max_grad) & small        # torch.norm over the single column (:435)
             split = (g >= max_grad) & ~small             # padded_grad of the clones is 0: never selected (:399-402)
+            if gate_opacity is not None:
+                gate = self.get_opacity.squeeze(1) > gate_opacity
+                clone, split = clone & gate, split & gate
             replay = decisions.get("replay") if decisions is not None else None
             if decisions is not None:
                 own = dict(clone=clone.cpu(), split=split.cpu(), g=g.detach().cpu().clone(), max_grad=float(max_grad),
@@ -648,25 +671,18 @@ class GaussianModelLite:
             raw = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
             new = {name: [raw[name][ci]] for name, _ in self.fields}
             if ns:
-                stds = scaling[si].repeat(N, 1)
-                if generator is None:
-                    generator = torch.Generator().manual_seed(0)
-                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(stds.device)
-                samples = noise * stds
-                rots = self.build_rotation(raw["rotation"][si]).repeat(N, 1, 1)
-                new_xyz = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + raw["xyz"][si].repeat(N, 1)
+                new_xyz, new_scaling = self._split_samples(raw["xyz"][si], scaling[si], raw["rotation"][si], N, generator)
                 new["xyz"].append(new_xyz)
-                new["scaling"].append(torch.log(scaling[si].repeat(N, 1) / (0.8 * N)))
+                new["scaling"].append(new_scaling)
                 for name, _ in self.fields:
                     if name not in ("xyz", "scaling"):
                         new[name].append(raw[name][si].repeat(N, 1))
             new = {name: torch.cat(v, dim=0) for name, v in new.items()}
-            n_new = new["xyz"].shape[0]
             # final prune (:455-462) evaluated on [survivors, clones, samples]
             keep_old = ~split
             op_all = torch.cat((torch.sigmoid(raw["opacity"][keep_old]), torch.sigmoid(new["opacity"])), dim=0).squeeze(1)
             prune = op_all < min_opacity
-            if max_screen_size:
+            if world_size_prune:
                 sc_all = torch.cat((max_scale[keep_old], torch.exp(new["scaling"]).max(dim=1).values), dim=0)
                 prune = prune | (sc_all > 0.1 * extent)  # big_points_vs is all-False (max_radii2D was just zeroed)
             if decisions is not None:
@@ -683,77 +699,106 @@ class GaussianModelLite:
             n_keep_old = int(keep_old.sum())
             src = keep_old.nonzero().squeeze(1)[~prune[:n_keep_old]]
             keep_new = ~prune[n_keep_old:]
-            new = {name: v[keep_new] for name, v in new.items()}
-            self._relayout(src, new)
-            if getattr(self, "spatial_order", False):   # the new rows go where their neighbours are
-                from . import synthetic
-                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            self._relayout(src, {name: v[keep_new] for name, v in new.items()})
+            self._restore_order_and_zero_statistics()
             return int(ci.numel()), ns, int(prune.sum())
+
+    def _split_samples(self, xyz, scales, rotation, N, generator):
+        """The N samples of each of the ns selected rows (their centres, ACTIVATED scales and raw rotations), drawn from the
+        row's own distribution (gaussian_model.py:404-412): centres R (noise * scale) + xyz and raw scaling log(scale / (0.8 N)),
+        both [N ns, 3] in the reference's repeat(N, 1) order.  One draw from the generator (_split_noise); ns > 0."""
+        stds = scales.repeat(N, 1)
+        samples = _split_noise(scales.shape[0], N, generator, stds.device) * stds
+        rots = self.build_rotation(rotation).repeat(N, 1, 1)
+        return torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + xyz.repeat(N, 1), torch.log(stds / (0.8 * N))
+
+    def _zero_statistics(self):
+        self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
+        self.denom = torch.zeros((self.P, 1), device=self.device)
+        self.max_radii2D = torch.zeros((self.P,), device=self.device)
+
+    def _restore_order_and_zero_statistics(self):
+        """The tail of every host rule: under spatial_order the new rows go where their neighbours are (an empty model has no
+        order to restore), then the statistics are zeroed at the new size (densification_postfix)."""
+        if getattr(self, "spatial_order", False) and self.P > 0:
+            from . import synthetic
+            self._relayout(synthetic.morton_order(self.params["xyz"]), {})
+        self._zero_statistics()
 
     def _densify_on_device(self, max_grad, min_opacity, extent, max_screen_size, generator, N, gate_opacity=None):
         """densify_and_prune from the kernels of csrc/gs_densify.hip (include/gsplat.h: gs_densify_plan / emit / gather,
         gs_morton_codes).  Returns (n_clone, n_split, n_pruned), or None - nothing written, the generator untouched - when every
         row would be pruned (the caller then takes the host path).  gate_opacity (DNGaussian's rule, _densify_dng_on_device):
         the plan is gs_densify_plan_gated's; everything behind it is unchanged."""
-        import ctypes as C
         opt = self.optimizer
         api, dev, P0 = opt.api, self.flat.device, self.P
         stream = _stream_of(self.flat)
         with torch.no_grad():
             raw = {name: self.params[name].detach() for name, _ in self.fields}
-            accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
-            if accum.numel() != P0 or denom.numel() != P0 or accum.dtype != torch.float32 or denom.dtype != torch.float32:
-                raise RuntimeError("densification statistics do not match the model")
-            # torch compares fp32 tensors with Python floats by rounding the scalar to fp32 ONCE: the products are formed in
-            # double as the host path forms them, then every threshold is rounded
-            f32 = lambda v: C.c_float(v).value   # noqa: E731
-            sample_div = f32(0.8 * N)
+            accum, denom = self._statistics_for_device()
+            sample_div = _f32(0.8 * N)
             nbytes = api.raw("densify_tmp_bytes")(P0)
             tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-            plan = [raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(), P0, N, f32(max_grad),
-                    f32(self.percent_dense * extent), f32(min_opacity), f32(0.1 * extent), sample_div, 1 if max_screen_size else 0]
+            plan = [raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(), P0, N, _f32(max_grad),
+                    _f32(self.percent_dense * extent), _f32(min_opacity), _f32(0.1 * extent), sample_div,
+                    1 if max_screen_size else 0]
             if gate_opacity is None:
                 api.call("densify_plan", *plan, tmp.data_ptr(), nbytes, stream)
             else:
-                api.call("densify_plan_gated", *plan, f32(gate_opacity), tmp.data_ptr(), nbytes, stream)
+                api.call("densify_plan_gated", *plan, _f32(gate_opacity), tmp.data_ptr(), nbytes, stream)
             # the ONE read-back: the counts size the new buffers and the noise (whose upload below blocks too, when rows split)
             n_keep, n_clone_keep, ns, ns_keep, n_clone = tmp[:20].view(torch.int32).cpu().tolist()
             P2 = n_keep + n_clone_keep + N * ns_keep
             if P2 == 0:
                 return None
-            noise = None
-            if ns:
-                if generator is None:
-                    generator = torch.Generator().manual_seed(0)
-                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
+            noise = _split_noise(ns, N, generator, dev)
             table = torch.empty((P2,), dtype=torch.int32, device=dev)
             new_xyz = torch.empty((P2, 3), dtype=torch.float32, device=dev)
             api.call("densify_emit", tmp.data_ptr(), nbytes, raw["xyz"].data_ptr(), raw["scaling"].data_ptr(),
                      raw["rotation"].data_ptr(), None if noise is None else noise.data_ptr(), P0, N, n_keep, n_clone_keep, ns,
                      ns_keep, P2, table.data_ptr(), new_xyz.data_ptr(), stream)
-            perm = None
-            if getattr(self, "spatial_order", False):   # synthetic.morton_order of the new centres, no read-back
-                lo, hi = torch.aminmax(new_xyz, dim=0)
-                codes = torch.empty((P2,), dtype=torch.int32, device=dev)
-                api.call("morton_codes", new_xyz.data_ptr(), P2, lo.data_ptr(), hi.data_ptr(), codes.data_ptr(), stream)
-                perm = torch.sort(codes, stable=True).indices
-            old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
-            names = [name for name, _ in self.fields]
-            widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
-            self._allocate(P2)
-            opt.alloc_moments()
-            api.call("densify_gather", None if perm is None else perm.data_ptr(), table.data_ptr(), new_xyz.data_ptr(), P2,
-                     old_flat.data_ptr(), old_m.data_ptr(), old_v.data_ptr(), P0, self.flat.data_ptr(), opt.exp_avg.data_ptr(),
-                     opt.exp_avg_sq.data_ptr(), len(names), widths, names.index("xyz"), names.index("scaling"), sample_div, stream)
-            for p in self.params.values():  # replaced tensors have no gradient until the next backward
-                p.grad = None
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            perm = self._morton_perm_on_device(new_xyz, stream)
+            self._gather_on_device("densify_gather", (perm, table, new_xyz), P2, sample_div, stream)
+            self._zero_statistics()
             return n_clone, ns, (P0 - ns - n_keep) + (n_clone - n_clone_keep) + N * (ns - ns_keep)
+
+    # ---- what the three device forms (_densify_on_device, _prune_on_device, _densify_fsgs_on_device) share
+    def _statistics_for_device(self, with_radii=False):
+        """xyz_gradient_accum and denom (and max_radii2D) as the kernels read them: contiguous fp32 of P elements on the model's
+        device."""
+        stats = [self.xyz_gradient_accum.contiguous(), self.denom.contiguous()]
+        if with_radii:
+            stats.append(self.max_radii2D.contiguous())
+        if any(t.numel() != self.P or t.dtype != torch.float32 or t.device != self.flat.device for t in stats):
+            raise RuntimeError("densification statistics do not match the model")
+        return stats
+
+    def _morton_perm_on_device(self, new_xyz, stream):
+        """synthetic.morton_order of the new centres (gs_morton_codes, a stable sort), no read-back; None without spatial_order."""
+        if not getattr(self, "spatial_order", False):
+            return None
+        P2 = new_xyz.shape[0]
+        lo, hi = torch.aminmax(new_xyz, dim=0)
+        codes = torch.empty((P2,), dtype=torch.int32, device=new_xyz.device)
+        self.optimizer.api.call("morton_codes", new_xyz.data_ptr(), P2, lo.data_ptr(), hi.data_ptr(), codes.data_ptr(), stream)
+        return torch.sort(codes, stable=True).indices
+
+    def _gather_on_device(self, entry, lead, P2, sample_div, stream, extra_fields=()):
+        """The one HBM pass of a device re-layout: new buffers of P2 rows, filled by the gather `entry` ("densify_gather" or
+        "densify_fsgs_gather") from the old ones.  lead: the entry's leading tensors (perm or None, table, [nb_kind,] new_xyz);
+        extra_fields: the fields the entry is told of behind xyz and scaling.  Every p.grad is None afterwards."""
+        import ctypes as C
+        opt, P0 = self.optimizer, self.P
+        old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
+        names = [name for name, _ in self.fields]
+        widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
+        self._allocate(P2)
+        opt.alloc_moments()
+        opt.api.call(entry, *[None if t is None else t.data_ptr() for t in lead], P2, old_flat.data_ptr(), old_m.data_ptr(),
+                     old_v.data_ptr(), P0, self.flat.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), len(names), widths,
+                     *[names.index(n) for n in ("xyz", "scaling") + tuple(extra_fields)], sample_div, stream)
+        for p in self.params.values():  # replaced tensors have no gradient until the next backward
+            p.grad = None
 
     # ------------------------------------------------------------------ DNGaussian: mask prunes and its densification rule
     def _require_device_form(self, what, entry):
@@ -803,14 +848,10 @@ class GaussianModelLite:
     def _prune_on_device(self, remove):
         """prune_points from gs_prune_plan / gs_prune_emit / gs_densify_gather.  `remove`: bool [P] on the model's device.
         Returns the number of rows removed, or None - nothing written - when every row would go."""
-        import ctypes as C
-        opt = self.optimizer
-        api, dev, P0 = opt.api, self.flat.device, self.P
+        api, dev, P0 = self.optimizer.api, self.flat.device, self.P
         stream = _stream_of(self.flat)
         remove = remove.contiguous()
-        stats = [self.xyz_gradient_accum.contiguous(), self.denom.contiguous(), self.max_radii2D.contiguous()]
-        if any(t.numel() != P0 or t.dtype != torch.float32 or t.device != dev for t in stats):
-            raise RuntimeError("densification statistics do not match the model")
+        stats = self._statistics_for_device(with_radii=True)
         nbytes = api.raw("prune_tmp_bytes")(P0)
         tmp = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
         api.call("prune_plan", remove.data_ptr(), P0, tmp.data_ptr(), nbytes, stream)
@@ -825,17 +866,8 @@ class GaussianModelLite:
         api.call("prune_emit", tmp.data_ptr(), nbytes, remove.data_ptr(), self.params["xyz"].detach().data_ptr(), P0, P2,
                  table.data_ptr(), new_xyz.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), stats[2].data_ptr(),
                  new_stats[0].data_ptr(), new_stats[1].data_ptr(), new_stats[2].data_ptr(), stream)
-        old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
-        names = [name for name, _ in self.fields]
-        widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
-        self._allocate(P2)
-        opt.alloc_moments()
-        # every row is a survivor: no sample, so the gather's sample_div is never read
-        api.call("densify_gather", None, table.data_ptr(), new_xyz.data_ptr(), P2, old_flat.data_ptr(), old_m.data_ptr(),
-                 old_v.data_ptr(), P0, self.flat.data_ptr(), opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), len(names), widths,
-                 names.index("xyz"), names.index("scaling"), 1.0, stream)
-        for p in self.params.values():  # replaced tensors have no gradient until the next backward
-            p.grad = None
+        # every row is a survivor, in its old order: no permutation, and no sample, so the gather's sample_div is never read
+        self._gather_on_device("densify_gather", (None, table, new_xyz), P2, 1.0, stream)
         self.xyz_gradient_accum, self.denom, self.max_radii2D = new_stats
         return P0 - P2
 
@@ -882,49 +914,8 @@ class GaussianModelLite:
             out = self._densify_dng_on_device(max_grad, min_opacity, extent, opa_thresh, generator, N)
             if out is not None:
                 return (n_outliers,) + out
-        with torch.no_grad():
-            P0 = self.P
-            grads = self.xyz_gradient_accum / self.denom
-            grads[grads.isnan()] = 0.0
-            g = grads.reshape(P0)
-            scaling = self.get_scaling
-            small = scaling.max(dim=1).values <= self.percent_dense * extent
-            gate = self.get_opacity.squeeze(1) > opa_thresh
-            clone = (g.abs() >= max_grad) & small & gate
-            split = (g >= max_grad) & ~small & gate      # padded_grad of the clones is 0: never selected
-            ci = clone.nonzero().squeeze(1)
-            si = split.nonzero().squeeze(1)
-            ns = int(si.numel())
-            raw = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
-            new = {name: [raw[name][ci]] for name, _ in self.fields}
-            if ns:
-                stds = scaling[si].repeat(N, 1)
-                if generator is None:
-                    generator = torch.Generator().manual_seed(0)
-                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(stds.device)
-                samples = noise * stds
-                rots = self.build_rotation(raw["rotation"][si]).repeat(N, 1, 1)
-                new["xyz"].append(torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + raw["xyz"][si].repeat(N, 1))
-                new["scaling"].append(torch.log(scaling[si].repeat(N, 1) / (0.8 * N)))
-                for name, _ in self.fields:
-                    if name not in ("xyz", "scaling"):
-                        new[name].append(raw[name][si].repeat(N, 1))
-            new = {name: torch.cat(v, dim=0) for name, v in new.items()}
-            # final prune (:518-523) evaluated on [survivors, clones, samples]: opacity only
-            keep_old = ~split
-            op_all = torch.cat((torch.sigmoid(raw["opacity"][keep_old]), torch.sigmoid(new["opacity"])), dim=0).squeeze(1)
-            prune = op_all < min_opacity
-            n_keep_old = int(keep_old.sum())
-            src = keep_old.nonzero().squeeze(1)[~prune[:n_keep_old]]
-            keep_new = ~prune[n_keep_old:]
-            self._relayout(src, {name: v[keep_new] for name, v in new.items()})
-            if getattr(self, "spatial_order", False) and self.P > 0:   # the new rows go where their neighbours are
-                from . import synthetic
-                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
-            return n_outliers, int(ci.numel()), ns, int(prune.sum())
+        # the final prune (:518-523) is opacity only: no world-size term, whatever max_screen_size is
+        return (n_outliers,) + self._clone_split_prune(max_grad, min_opacity, extent, False, opa_thresh, generator, N)
 
     def _densify_dng_on_device(self, max_grad, min_opacity, extent, opa_thresh, generator, N):
         """Steps 2-6 of densify_and_prune_dng from the kernels: _densify_on_device with the gated plan and no size test.
@@ -945,26 +936,28 @@ class GaussianModelLite:
         api: whose kNN to use (default: the optimizer's).  Returns the number of new rows."""
         if self.with_nir:
             raise NotImplementedError("proximity: the multispectral model has no rule for the new rows' NIR albedo")
-        from .knn import dist2_with_indices
         with torch.no_grad():
             P0 = self.P
             raw = {name: self.params[name].detach().reshape(P0, n) for name, n in self.fields}
-            dist, nearest = dist2_with_indices(api or self.optimizer.api, raw["xyz"])
-            sel = torch.logical_and(dist > (5. * extent), torch.max(self.get_scaling, dim=1).values > extent)
-            new_idx = nearest[sel].reshape(-1).long()
-            source_xyz = raw["xyz"][sel].repeat(1, 3, 1).reshape(-1, 3)
-            new = {"xyz": (source_xyz + raw["xyz"][new_idx]) / 2, "scaling": raw["scaling"][new_idx],
-                   "opacity": raw["opacity"][new_idx], "features": torch.zeros_like(raw["features"][new_idx])}
-            new["rotation"] = torch.zeros_like(raw["rotation"][new_idx])
-            new["rotation"][:, 0] = 1
+            new = self._proximity_rows(raw, extent, api or self.optimizer.api)
             self._relayout(torch.arange(P0, device=raw["xyz"].device), new)
-            if getattr(self, "spatial_order", False):
-                from . import synthetic
-                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
-            return int(new_idx.numel())
+            self._restore_order_and_zero_statistics()
+            return int(new["xyz"].shape[0])
+
+    @staticmethod
+    def _proximity_rows(rows, extent, knn_api):
+        """The rows proximity()'s rule adds to the set `rows` (field -> [n, w], raw values), as proximity()'s docstring states it,
+        the tiled repeat(1, 3, 1) of the selected centres as the reference writes it: field -> [3 S, w]."""
+        from .knn import dist2_with_indices
+        dist, nearest = dist2_with_indices(knn_api, rows["xyz"])
+        sel = torch.logical_and(dist > (5. * extent), torch.max(torch.exp(rows["scaling"]), dim=1).values > extent)
+        new_idx = nearest[sel].reshape(-1).long()
+        source_xyz = rows["xyz"][sel].repeat(1, 3, 1).reshape(-1, 3)
+        new = {"xyz": (source_xyz + rows["xyz"][new_idx]) / 2, "scaling": rows["scaling"][new_idx],
+               "opacity": rows["opacity"][new_idx], "features": torch.zeros_like(rows["features"][new_idx])}
+        new["rotation"] = torch.zeros_like(rows["rotation"][new_idx])
+        new["rotation"][:, 0] = 1
+        return new
 
     def densify_and_prune_fsgs(self, max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres=10.0,
                                prune_from_iter=500, proximity_until_iter=2000, generator=None, N=2, api=None, on_device=False):
@@ -995,10 +988,7 @@ class GaussianModelLite:
         if self.with_nir:
             raise NotImplementedError("densify_and_prune_fsgs: the multispectral model has no rule for the new rows' NIR albedo")
         if on_device:
-            dev_api = getattr(self.optimizer, "api", None)
-            if not (self.flat.is_cuda and isinstance(self.optimizer, FlatAdam) and hasattr(dev_api, "_densify_fsgs_plan")):
-                raise RuntimeError("densify_and_prune_fsgs(on_device=True) needs a GPU model built with the HIP api (flat Adam "
-                                   "state); there is no fallback")
+            self._require_device_form("densify_and_prune_fsgs", "densify_fsgs_plan")
             out = self._densify_fsgs_on_device(max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres,
                                                prune_from_iter, proximity_until_iter, generator, N)
             if out is not None:
@@ -1037,15 +1027,8 @@ class GaussianModelLite:
             split = split | ((dist > dist_thres * extent) & (max_scale > extent))
             ns = int(split.sum())
             if ns:
-                stds = act[split].repeat(N, 1)
-                if generator is None:
-                    generator = torch.Generator().manual_seed(0)
-                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
-                samples = noise * stds
-                rots = self.build_rotation(cur["rotation"][split]).repeat(N, 1, 1)
                 new = {name: v[split].repeat(N, 1) for name, v in cur.items()}
-                new["xyz"] = torch.bmm(rots, samples.unsqueeze(-1)).squeeze(-1) + cur["xyz"][split].repeat(N, 1)
-                new["scaling"] = torch.log(act[split].repeat(N, 1) / (0.8 * N))
+                new["xyz"], new["scaling"] = self._split_samples(cur["xyz"][split], act[split], cur["rotation"][split], N, generator)
                 cur, origin = append(cur, origin, new)
                 if pruning:
                     keep = ~torch.cat((split, torch.zeros((N * ns,), dtype=torch.bool, device=dev)))
@@ -1054,15 +1037,8 @@ class GaussianModelLite:
             # proximity (:405-420) on the set as it stands
             n_prox = 0
             if iteration < proximity_until_iter:
-                dist, nearest = dist2_with_indices(knn_api, cur["xyz"])
-                sel = torch.logical_and(dist > (5. * extent), torch.max(torch.exp(cur["scaling"]), dim=1).values > extent)
-                new_idx = nearest[sel].reshape(-1).long()
-                source_xyz = cur["xyz"][sel].repeat(1, 3, 1).reshape(-1, 3)
-                new = {"xyz": (source_xyz + cur["xyz"][new_idx]) / 2, "scaling": cur["scaling"][new_idx],
-                       "opacity": cur["opacity"][new_idx], "features": torch.zeros_like(cur["features"][new_idx])}
-                new["rotation"] = torch.zeros_like(cur["rotation"][new_idx])
-                new["rotation"][:, 0] = 1
-                n_prox = int(new_idx.numel())
+                new = self._proximity_rows(cur, extent, knn_api)
+                n_prox = int(new["xyz"].shape[0])
                 cur, origin = append(cur, origin, new)
             # the final prune (:484-490)
             prune = (torch.sigmoid(cur["opacity"]) < min_opacity).squeeze(1)
@@ -1074,12 +1050,7 @@ class GaussianModelLite:
                 n_pruned += int(prune.sum())
             old = origin >= 0     # rows of the model come first, in their order: nothing above reorders
             self._relayout(origin[old], {name: v[~old] for name, v in cur.items()})
-            if getattr(self, "spatial_order", False) and self.P:
-                from . import synthetic
-                self._relayout(synthetic.morton_order(self.params["xyz"]), {})
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            self._restore_order_and_zero_statistics()
             return n_clone, ns, n_prox, n_pruned
 
     def _densify_fsgs_on_device(self, max_grad, min_opacity, extent, max_screen_size, iteration, dist_thres, prune_from_iter,
@@ -1088,21 +1059,16 @@ class GaussianModelLite:
         searches from gs_knn_mean_dist2_idx.  Three read-backs (two without proximity), each one small copy.  Returns the
         4-tuple, or None - nothing written, the generator untouched - when a kNN stage would hold fewer than 4 points, every row
         would be pruned or percent_dense > 1 (a clone could then be split); the caller takes the host path."""
-        import ctypes as C
         if self.percent_dense > 1:
             return None
-        opt = self.optimizer
-        api, dev, P0 = opt.api, self.flat.device, self.P
+        api, dev, P0 = self.optimizer.api, self.flat.device, self.P
         if P0 < 1:
             return None
         stream = _stream_of(self.flat)
         with torch.no_grad():
             raw = {name: self.params[name].detach() for name, _ in self.fields}
-            accum, denom = self.xyz_gradient_accum.contiguous(), self.denom.contiguous()
-            if accum.numel() != P0 or denom.numel() != P0 or accum.dtype != torch.float32 or denom.dtype != torch.float32:
-                raise RuntimeError("densification statistics do not match the model")
-            f32 = lambda v: C.c_float(v).value   # noqa: E731  (products in double, rounded once: what torch compares with)
-            sample_div = f32(0.8 * N)
+            accum, denom = self._statistics_for_device()
+            sample_div = _f32(0.8 * N)
             prune_on = 1 if iteration > prune_from_iter else 0
             proximity = iteration < proximity_until_iter
             u8 = lambda n: torch.empty((n,), dtype=torch.uint8, device=dev)   # noqa: E731
@@ -1120,25 +1086,21 @@ class GaussianModelLite:
             tmp = u8(nbytes)
             xyz1 = torch.empty((2 * P0, 3), dtype=torch.float32, device=dev)
             api.call("densify_fsgs_plan", raw["scaling"].data_ptr(), raw["opacity"].data_ptr(), accum.data_ptr(), denom.data_ptr(),
-                     raw["xyz"].data_ptr(), P0, N, f32(max_grad), f32(self.percent_dense * extent), f32(min_opacity),
-                     f32(0.1 * extent), f32(extent), sample_div, 1 if max_screen_size else 0, tmp.data_ptr(), nbytes,
+                     raw["xyz"].data_ptr(), P0, N, _f32(max_grad), _f32(self.percent_dense * extent), _f32(min_opacity),
+                     _f32(0.1 * extent), _f32(extent), sample_div, 1 if max_screen_size else 0, tmp.data_ptr(), nbytes,
                      xyz1.data_ptr(), stream)
             n_clone = int(tmp[:4].view(torch.int32).cpu())                                   # read-back 1
             if P0 + n_clone < 4:
                 return None
             dist1, _ = knn(xyz1, P0 + n_clone, False)
-            api.call("densify_fsgs_merge", tmp.data_ptr(), nbytes, dist1.data_ptr(), P0, f32(dist_thres * extent), prune_on, stream)
+            api.call("densify_fsgs_merge", tmp.data_ptr(), nbytes, dist1.data_ptr(), P0, _f32(dist_thres * extent), prune_on, stream)
             ns, n_stay, keep_old, keep_clone, keep_split = tmp[32:52].view(torch.int32).cpu().tolist()   # read-back 2
             nQ = n_stay + n_clone + N * ns
             n_keep_q = keep_old + keep_clone + N * keep_split
             # a proximity row is kept exactly when its neighbour, a row of Q, is: nothing kept in Q = nothing kept at all
             if n_keep_q == 0 or (proximity and nQ < 4):
                 return None
-            noise = None
-            if ns:
-                if generator is None:
-                    generator = torch.Generator().manual_seed(0)
-                noise = torch.randn((ns * N, 3), generator=generator, dtype=torch.float32).to(dev)
+            noise = _split_noise(ns, N, generator, dev)
             table_q = torch.empty((nQ,), dtype=torch.int32, device=dev)
             xyz_q = torch.empty((nQ, 3), dtype=torch.float32, device=dev)
             api.call("densify_fsgs_emit", tmp.data_ptr(), nbytes, raw["xyz"].data_ptr(), raw["scaling"].data_ptr(),
@@ -1149,7 +1111,7 @@ class GaussianModelLite:
             tmp_q = u8(qbytes)
             api.call("densify_fsgs_prox_plan", tmp.data_ptr(), nbytes, P0, table_q.data_ptr(), nQ,
                      None if dist2 is None else dist2.data_ptr(), None if nearest is None else nearest.data_ptr(),
-                     f32(5. * extent), prune_on, tmp_q.data_ptr(), qbytes, stream)
+                     _f32(5. * extent), prune_on, tmp_q.data_ptr(), qbytes, stream)
             S, n_keep_prox = 0, 0
             if proximity:
                 _, S, k0, k1, k2 = tmp_q[:20].view(torch.int32).cpu().tolist()              # read-back 3
@@ -1162,26 +1124,10 @@ class GaussianModelLite:
             api.call("densify_fsgs_final", tmp_q.data_ptr(), qbytes, table_q.data_ptr(), xyz_q.data_ptr(),
                      None if nearest is None else nearest.data_ptr(), nQ, n_keep_q, S, n_keep_prox, P2, table.data_ptr(),
                      nb_kind.data_ptr(), new_xyz.data_ptr(), sel_rows[0].data_ptr(), sel_rows[1].data_ptr(), stream)
-            perm = None
-            if getattr(self, "spatial_order", False):
-                lo, hi = torch.aminmax(new_xyz, dim=0)
-                codes = torch.empty((P2,), dtype=torch.int32, device=dev)
-                api.call("morton_codes", new_xyz.data_ptr(), P2, lo.data_ptr(), hi.data_ptr(), codes.data_ptr(), stream)
-                perm = torch.sort(codes, stable=True).indices
-            old_flat, old_m, old_v = self.flat, opt.exp_avg, opt.exp_avg_sq   # (alive until the gather has been enqueued)
-            names = [name for name, _ in self.fields]
-            widths = (C.c_int32 * len(names))(*[n for _, n in self.fields])
-            self._allocate(P2)
-            opt.alloc_moments()
-            api.call("densify_fsgs_gather", None if perm is None else perm.data_ptr(), table.data_ptr(), nb_kind.data_ptr(),
-                     new_xyz.data_ptr(), P2, old_flat.data_ptr(), old_m.data_ptr(), old_v.data_ptr(), P0, self.flat.data_ptr(),
-                     opt.exp_avg.data_ptr(), opt.exp_avg_sq.data_ptr(), len(names), widths, names.index("xyz"),
-                     names.index("scaling"), names.index("opacity"), names.index("rotation"), sample_div, stream)
-            for p in self.params.values():
-                p.grad = None
-            self.xyz_gradient_accum = torch.zeros((self.P, 1), device=self.device)
-            self.denom = torch.zeros((self.P, 1), device=self.device)
-            self.max_radii2D = torch.zeros((self.P,), device=self.device)
+            perm = self._morton_perm_on_device(new_xyz, stream)
+            self._gather_on_device("densify_fsgs_gather", (perm, table, nb_kind, new_xyz), P2, sample_div, stream,
+                                   extra_fields=("opacity", "rotation"))
+            self._zero_statistics()
             n_pruned = (ns + (nQ + 3 * S - P2)) if prune_on else 0
             return n_clone, ns, 3 * S, n_pruned
 
@@ -1562,29 +1508,35 @@ class Trainer:
         if will_densify:
             self.gather_optimizer_state()
             thr = opt.size_threshold if iteration > opt.opacity_reset_interval else None
-            gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
             # (densify_decisions: parity instrument, see GaussianModelLite.densify_and_prune - a callable iteration -> dict)
             dec = self.densify_decisions(iteration) if self.densify_decisions is not None else None
-            rule = getattr(opt, "densify_rule", "3dgs")
-            if rule == "fsgs":   # FSGS/train.py:166: size_threshold = None; -> (n_clone, n_split, n_proximity, n_pruned)
-                densified = m.densify_and_prune_fsgs(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
-                                                     iteration, dist_thres=opt.dist_thres, prune_from_iter=opt.prune_from_iter,
-                                                     proximity_until_iter=opt.proximity_until_iter, generator=gen,
-                                                     on_device=bool(getattr(opt, "densify_on_device", False)))
-            elif rule == "3dgs":
-                densified = m.densify_and_prune(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, thr,
-                                                self.last["radii"], generator=gen, decisions=dec,
-                                                on_device=bool(getattr(opt, "densify_on_device", False)))
-            elif rule == "dng":   # DNGaussian/train_llff.py:199-201: size_threshold = max_dist = None; -> its 4-tuple
-                densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
-                                                    opt.split_opacity_thresh, None, generator=gen,
-                                                    on_device=opt.densify_on_device)
-            else:
-                raise ValueError("densify_rule must be '3dgs', 'fsgs' or 'dng'")
+            densified = self._densify(iteration, opt, opt.min_opacity, thr, radii=self.last["radii"], decisions=dec)
         if will_reset:
             m.reset_opacity()
             reset = True
         return dict(loss=loss, densified=densified, reset=reset, P=m.P, camera=ci)
+
+    def _densify(self, iteration, opt, min_opacity, max_screen_size, rule=None, radii=None, decisions=None):
+        """The densification of `iteration` by the rule opt.densify_rule names (or `rule`: a trainer of one method uses that
+        method's rule whatever the options say), with the iteration's own CPU generator
+        (opt.seed, iteration: every rank draws the same noise) -> what the rule returns.  min_opacity and max_screen_size are the
+        caller's; FSGS (FSGS/train.py:166) and DNGaussian (DNGaussian/train_llff.py:199-201) take size_threshold = None, and
+        DNGaussian max_dist = None."""
+        m = self.model
+        gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
+        on_device = bool(getattr(opt, "densify_on_device", False))
+        rule = rule or getattr(opt, "densify_rule", "3dgs")
+        if rule == "fsgs":   # -> (n_clone, n_split, n_proximity, n_pruned)
+            return m.densify_and_prune_fsgs(opt.densify_grad_threshold, min_opacity, opt.cameras_extent, None, iteration,
+                                            dist_thres=opt.dist_thres, prune_from_iter=opt.prune_from_iter,
+                                            proximity_until_iter=opt.proximity_until_iter, generator=gen, on_device=on_device)
+        if rule == "3dgs":   # -> (n_clone, n_split, n_pruned)
+            return m.densify_and_prune(opt.densify_grad_threshold, min_opacity, opt.cameras_extent, max_screen_size, radii,
+                                       generator=gen, decisions=decisions, on_device=on_device)
+        if rule == "dng":   # -> (n_outliers, n_clone, n_split, n_pruned)
+            return m.densify_and_prune_dng(opt.densify_grad_threshold, min_opacity, opt.cameras_extent, None,
+                                           opt.split_opacity_thresh, None, generator=gen, on_device=on_device)
+        raise ValueError("densify_rule must be '3dgs', 'fsgs' or 'dng'")
 
     def _draw_background(self, seed):
         """A fresh rand(3) into the one persistent background buffer (allocated, with a generator seeded from seed + rank on
@@ -2719,11 +2671,7 @@ class TrainerFSGS(Trainer):
             self.depth_weight = opt.late_depth_weight
         densified = None
         if will_densify:
-            gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
-            densified = m.densify_and_prune_fsgs(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
-                                                 iteration, dist_thres=opt.dist_thres, prune_from_iter=opt.prune_from_iter,
-                                                 proximity_until_iter=opt.proximity_until_iter, generator=gen,
-                                                 on_device=bool(opt.densify_on_device))
+            densified = self._densify(iteration, opt, opt.min_opacity, None, rule="fsgs")
         m.update_learning_rate(iteration, opt.position_lr_final, opt.position_lr_delay_mult, opt.position_lr_max_steps)
         reset = (iteration - opt.start_sample_pseudo - 1) % opt.opacity_reset_interval == 0 and iteration > opt.start_sample_pseudo
         if reset:
@@ -3131,10 +3079,7 @@ class TrainerDNG(Trainer):
                 m.update_view_statistics(pkg["radii"], pkg["viewspace_points"].grad)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
                     self._before_densify(iteration, opt, pkg)
-                    gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
-                    densified = m.densify_and_prune_dng(opt.densify_grad_threshold, opt.min_opacity, opt.cameras_extent, None,
-                                                        opt.split_opacity_thresh, None, generator=gen,
-                                                        on_device=bool(opt.densify_on_device))
+                    densified = self._densify(iteration, opt, opt.min_opacity, None, rule="dng")
                     self._after_densify(iteration, opt)
                     relayout = True
             if self._near_prune_due(iteration, opt):
@@ -3649,9 +3594,7 @@ class TrainerDNGBlenderSH(TrainerDNG):
                 m.update_view_statistics(pkg["radii"], pkg["viewspace_points"].grad)
                 if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
                     thr = opt.size_threshold if iteration > opt.opacity_reset_interval else None
-                    gen = torch.Generator().manual_seed(opt.seed * 1000003 + iteration)
-                    densified = m.densify_and_prune(opt.densify_grad_threshold, opt.prune_opacity, opt.cameras_extent, thr,
-                                                    generator=gen, on_device=bool(opt.densify_on_device))
+                    densified = self._densify(iteration, opt, opt.prune_opacity, thr, rule="3dgs")
                     if opt.white_rule is not None:
                         rule_thr, factor = opt.white_rule
                         rule_count, self.last_colour = self._white_rule_sh(

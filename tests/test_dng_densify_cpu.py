@@ -125,6 +125,28 @@ def test_the_spatial_order_is_restored_after_a_densification(oracle, P):
                 assert torch.equal(dg.bits(part_so[n]), dg.bits(part_flat[n][perm])), n
 
 
+@pytest.mark.parametrize("spatial_order", (False, True))
+@pytest.mark.parametrize("P", (1, 70, 257))
+def test_with_the_gate_open_and_no_size_test_it_is_the_3dgs_rule(oracle, P, spatial_order):
+    """opa_thresh below every opacity and max_screen_size = None (no world-size term on the 3DGS side either): without the
+    outlier prune densify_and_prune_dng and densify_and_prune are one body - the same counts, the same draws, the same model bit
+    for bit."""
+    a, b = (dg.build_model(oracle.api, "cpu", P, 7, spatial_order=spatial_order) for _ in range(2))
+    assert float(a.get_opacity.detach().min()) > -1.0
+    ga, gb = torch.Generator().manual_seed(3), torch.Generator().manual_seed(3)
+    ra = a.densify_and_prune_dng(dg.MAX_GRAD, dg.MIN_OPACITY, dg.EXTENT, None, -1.0, max_dist=None, generator=ga)
+    rb = b.densify_and_prune(dg.MAX_GRAD, dg.MIN_OPACITY, dg.EXTENT, None, generator=gb)
+    assert ra == (0,) + rb and a.P == b.P
+    assert torch.equal(ga.get_state(), gb.get_state())
+    if P >= 70:
+        assert all(c > 0 for c in rb) and a.P > 0
+    for part_a, part_b in zip(dg.snapshot(a), dg.snapshot(b)):
+        for n in part_b:
+            assert part_a[n].shape == part_b[n].shape and torch.equal(dg.bits(part_a[n]), dg.bits(part_b[n])), n
+    for sa, sb in zip(dg.statistics(a), dg.statistics(b)):
+        assert sa.shape == sb.shape and torch.equal(dg.bits(sa), dg.bits(sb))
+
+
 @pytest.mark.parametrize("with_nir", (False, True))
 @pytest.mark.parametrize("P", dg.SIZES)
 def test_the_device_form_restated_is_the_host_path(oracle, P, with_nir):

@@ -119,6 +119,32 @@ def test_proximity_inside_the_call_reproduces_the_tiling(oracle):
     assert own < 3 * S
 
 
+@pytest.mark.parametrize("spatial_order", (False, True))
+@pytest.mark.parametrize("S", (1, 3))
+def test_proximity_alone_is_the_proximity_stage_of_the_call(oracle, S, spatial_order):
+    """proximity() and densify_and_prune_fsgs with nothing to clone (statistic 0 against max_grad 1), nothing to split (the
+    distance rule's bound out of reach) and no prune (iteration <= prune_from_iter) append the same rows, bit for bit: with one
+    selected row and with three, the tiling case.  The extent is placed midway between the S-th and the (S+1)-th largest of the
+    rows' min(dist / 5, max scale), so exactly S rows pass both of the rule's comparisons."""
+    a, b = (fr.build_model(oracle.api, "cpu", 257, spatial_order=spatial_order) for _ in range(2))
+    for m in (a, b):
+        m.xyz_gradient_accum.zero_()
+        m.denom.fill_(1.0)
+    dist, _ = dist2_with_indices(oracle.api, a.params["xyz"].detach())
+    v = torch.minimum(dist / 5, a.get_scaling.detach().max(dim=1).values).sort(descending=True).values
+    assert float(v[S - 1]) > float(v[S]) * (1 + 1e-3)
+    extent = (float(v[S - 1]) + float(v[S])) / 2
+    gen = torch.Generator().manual_seed(77)
+    n = a.proximity(extent)
+    counts = b.densify_and_prune_fsgs(1.0, 0.0, extent, None, 400, dist_thres=1e6, prune_from_iter=500, proximity_until_iter=2000,
+                                      generator=gen)
+    assert counts == (0, 0, n, 0) and n == 3 * S and a.P == b.P == 257 + n
+    assert torch.equal(gen.get_state(), torch.Generator().manual_seed(77).get_state())
+    for part_a, part_b in zip(fr.snapshot(a), fr.snapshot(b)):
+        for k in part_a:
+            assert torch.equal(fr.bits(part_a[k]), fr.bits(part_b[k])), k
+
+
 def test_with_nir_raises(oracle):
     m = GaussianModelLite(synthetic.trained_like(64, seed=0), torch.device("cpu"), api=oracle.api, with_nir=True)
     with pytest.raises(NotImplementedError):

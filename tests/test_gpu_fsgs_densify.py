@@ -197,6 +197,78 @@ def test_abi_errors_touch_no_memory(hip):
     assert int((kind != 0x5A).sum()) == 0
 
 
+GATHER_P, PROXIMITY = 257, 3
+MODEL_WIDTHS, ODD_WIDTHS = (3, 48, 1, 3, 4), (3, 5, 1, 3, 4)   # (5: no constant-width instantiation, the run-time width)
+SENTINEL = 0x7FC12345                                          # a NaN no gather computes or copies
+
+
+def run_both_gathers(hip, P2, with_perm, widths, prox_at=None):
+    """gs_densify_gather and gs_densify_fsgs_gather (all-zero nb_kind) on one table of P2 entries over GATHER_P source rows, from
+    CPU generators -> the two (flat, exp_avg, exp_avg_sq) triples as int32 bits [P2 * sum(widths)], and the permutation."""
+    api, P, W = hip.api, GATHER_P, sum(widths)
+    g = torch.Generator().manual_seed(1000 * P2 + len(widths) + 7 * with_perm)
+    old = [torch.randn((P * W,), generator=g).to(DEV) for _ in range(3)]
+    src = torch.randint(0, P, (P2,), generator=g)
+    kind = torch.randint(0, PROXIMITY, (P2,), generator=g)            # survivor, clone, sample
+    if P2 >= 3:
+        kind[:3] = torch.arange(3)                                    # (each of them at least once)
+    if prox_at is not None:
+        kind[prox_at] = PROXIMITY
+    entry = src | (kind << 30)
+    table = torch.where(entry >= 2 ** 31, entry - 2 ** 32, entry).to(torch.int32).to(DEV)   # (the uint32's bits)
+    new_xyz = torch.randn((P2, 3), generator=g).to(DEV)
+    perm = torch.randperm(P2, generator=g).to(DEV) if with_perm else None
+    nb_kind = torch.zeros((P2,), dtype=torch.uint8, device=DEV)
+    cw = (C.c_int32 * len(widths))(*widths)
+    outs = []
+    for entry in ("densify_gather", "densify_fsgs_gather"):
+        new = [torch.full((P2 * W,), SENTINEL, dtype=torch.int32, device=DEV) for _ in range(3)]
+        lead = [None if perm is None else perm.data_ptr(), table.data_ptr()]
+        tail = [0, 3]
+        if entry == "densify_fsgs_gather":
+            lead.append(nb_kind.data_ptr())
+            tail += [2, 4]
+        rc = api.raw(entry)(*lead, new_xyz.data_ptr(), P2, old[0].data_ptr(), old[1].data_ptr(), old[2].data_ptr(), P,
+                            new[0].data_ptr(), new[1].data_ptr(), new[2].data_ptr(), len(widths), cw, *tail, 1.6, None)
+        assert rc == 0, (entry, rc)
+        outs.append(new)
+    torch.cuda.synchronize()
+    return outs[0], outs[1], perm
+
+
+def rows_of(buf, P2, widths):
+    """[P2, sum(widths)]: the field-major buffer's rows side by side."""
+    parts, off = [], 0
+    for w in widths:
+        parts.append(buf[off:off + P2 * w].view(P2, w))
+        off += P2 * w
+    return torch.cat(parts, dim=1)
+
+
+@pytest.mark.parametrize("widths", (MODEL_WIDTHS, ODD_WIDTHS))
+@pytest.mark.parametrize("with_perm", (False, True))
+@pytest.mark.parametrize("P2", (1, 255, 257))
+def test_the_two_gathers_are_one_kernel_body(hip, P2, with_perm, widths):
+    """A table of survivors, clones and samples only: both entry points write the same bytes into parameters and both moments,
+    and every one of them."""
+    plain, fsgs, _ = run_both_gathers(hip, P2, with_perm, widths)
+    for a, b in zip(plain, fsgs):
+        assert torch.equal(a, b) and int((a == SENTINEL).sum()) == 0
+
+
+def test_only_the_fsgs_gather_writes_a_proximity_row(hip):
+    """One GS_DENSIFY_PROXIMITY entry: gs_densify_gather, which has no neighbour kinds, drops it - that output row keeps its
+    sentinel in every field of all three buffers - and gs_densify_fsgs_gather writes the row; the other rows are the same."""
+    P2, at = 257, 100
+    plain, fsgs, perm = run_both_gathers(hip, P2, True, MODEL_WIDTHS, prox_at=at)
+    row = int((perm == at).nonzero())
+    others = torch.arange(P2, device=DEV) != row
+    for a, b in zip(plain, fsgs):
+        a, b = rows_of(a, P2, MODEL_WIDTHS), rows_of(b, P2, MODEL_WIDTHS)
+        assert torch.equal(a[others], b[others]) and int((a[others] == SENTINEL).sum()) == 0
+        assert int((a[row] != SENTINEL).sum()) == 0 and int((b[row] == SENTINEL).sum()) == 0
+
+
 def conditions_hold(hip, m, it, N=2, screen=None, **kw):
     """The input conditions of tests/test_fsgs_densify_cpu.py on a model the CPU test cannot rebuild (a trained one)."""
     state = fr.snapshot(m)
