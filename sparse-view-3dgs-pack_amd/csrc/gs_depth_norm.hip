@@ -27,6 +27,7 @@
 // patch.  The p column sums of a patch meet in LDS and are added by the patch's first lane in column order.  No float
 // atomics, no host synchronisation: every sum has one fixed order.
 #include "gs_common.h"
+#include "gs_reduce.h"
 
 namespace {
 
@@ -125,7 +126,9 @@ __device__ __forceinline__ float dn_edge_w(const float* img, int C, size_t plane
 }
 __device__ __forceinline__ float dn_sign(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
 
-// v[q] of the lanes [t0, t0 + span) -> their sum, in lane order, at the lane `lead` (t == t0); sh: [NQ][GS_BLOCK]
+// v[q] of the lanes [t0, t0 + span) -> their sum, in lane order, at the lane `lead` (t == t0); sh: [NQ][GS_BLOCK].  A patch's
+// lanes are a segment of the workgroup, not the whole of it, and the patch record's bits are this serial order: it is NOT
+// gs_reduce.h's tree and stays here on purpose.
 template <int NQ>
 __device__ __forceinline__ void dn_segment_sum(double (&v)[NQ], double* sh, int t, bool lead, int span) {
   for (int q = 0; q < NQ; q++) sh[q * GS_BLOCK + t] = v[q];
@@ -136,20 +139,6 @@ __device__ __forceinline__ void dn_segment_sum(double (&v)[NQ], double* sh, int 
       for (int i = 0; i < span; i++) a += sh[q * GS_BLOCK + t + i];
       v[q] = a;
     }
-  __syncthreads();
-}
-
-// sum over the workgroup, fixed tree; every lane gets the result.  sh: [NQ][GS_BLOCK]
-template <int NQ>
-__device__ __forceinline__ void dn_block_sum(double (&v)[NQ], double* sh, int t) {
-  for (int q = 0; q < NQ; q++) sh[q * GS_BLOCK + t] = v[q];
-  __syncthreads();
-  for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w)
-      for (int q = 0; q < NQ; q++) sh[q * GS_BLOCK + t] += sh[q * GS_BLOCK + t + w];
-    __syncthreads();
-  }
-  for (int q = 0; q < NQ; q++) v[q] = sh[q * GS_BLOCK];
   __syncthreads();
 }
 
@@ -256,7 +245,7 @@ __global__ __launch_bounds__(GS_BLOCK) void dn_stats_kernel(DnArgs a) {
       }
     }
   }
-  dn_block_sum<DN_IP>(v, sh_p, t);
+  gs_block_tree_sum<GS_BLOCK>(v, sh_p, t);
   if (t < DN_IP) a.ipart[(size_t)b * DN_IP + t] = v[t];
 }
 
@@ -264,10 +253,9 @@ __global__ __launch_bounds__(GS_BLOCK) void dn_globals_kernel(DnArgs a) {
   __shared__ double sh[DN_SP * GS_BLOCK];
   const int t = threadIdx.x;
   if (a.need_S || a.smooth) {
-    double v[DN_IP] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = t; i < a.nimg; i += GS_BLOCK)
-      for (int q = 0; q < DN_IP; q++) v[q] += a.ipart[(size_t)i * DN_IP + q];
-    dn_block_sum<DN_IP>(v, sh, t);
+    double v[DN_IP];
+    gs_partials_tree_sum<GS_BLOCK>(a.ipart, a.nimg, v, sh, t);
+    __syncthreads();  // sh is written again below
     if (t == 0) {
       const double N = (double)a.H * a.W;
       a.g->S_x = (float)sqrt(fmax(v[1] - v[0] * v[0] / N, 0.0) / (N - 1.0));
@@ -282,10 +270,9 @@ __global__ __launch_bounds__(GS_BLOCK) void dn_globals_kernel(DnArgs a) {
   for (int k = 0; k < 2; k++) {
     const DnTerm& tm = a.term[k];
     if (!tm.on) continue;
-    double v[DN_SP] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = t; i < tm.nwg; i += GS_BLOCK)
-      for (int q = 0; q < DN_SP; q++) v[q] += tm.spart[(size_t)i * DN_SP + q];
-    dn_block_sum<DN_SP>(v, sh, t);
+    double v[DN_SP];
+    gs_partials_tree_sum<GS_BLOCK>(tm.spart, tm.nwg, v, sh, t);
+    __syncthreads();  // sh is written again by the next term
     if (t == 0) {
       const double L = (double)tm.Lx * tm.Ly, n = (double)tm.p * tm.p, N = L * n;
       const double ssx = v[2] + n * fmax(v[1] - v[0] * v[0] / L, 0.0);
@@ -363,10 +350,9 @@ __global__ __launch_bounds__(GS_BLOCK) void dn_finish_kernel(DnArgs a, int mode,
       if (t == 0) { a.g->cnt[k] = 0.0; a.g->T[k] = 0.0; a.g->loss[1 + k] = 0.f; }
       continue;
     }
-    double v[DN_AP] = {0.0, 0.0, 0.0};
-    for (int i = t; i < tm.nwg; i += GS_BLOCK)
-      for (int q = 0; q < DN_AP; q++) v[q] += tm.apart[(size_t)i * DN_AP + q];
-    dn_block_sum<DN_AP>(v, sh, t);
+    double v[DN_AP];
+    gs_partials_tree_sum<GS_BLOCK>(tm.apart, tm.nwg, v, sh, t);
+    __syncthreads();  // sh is written again by the next term
     loss[k] = (float)(v[1] / v[0]);  // 0 / 0 = NaN on an empty mask: the reference's mean over no elements
     if (t == 0) {
       a.g->cnt[k] = v[0];

@@ -177,47 +177,8 @@ int launch_depth_fwd(const uint2* ranges, const uint32_t* point_list, int W, int
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// backward blend.  The reduction primitives are gs_render_bwd_wave.hip's, copied: that file's generated code stays as it is.
+// backward blend (the cross-lane sums are gs_blend.h's)
 // ------------------------------------------------------------------------------------------------------------------
-template <int CTRL, int ROW_MASK, bool BOUND>
-__device__ __forceinline__ float dp_dppw(float v) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xf, BOUND));
-}
-typedef unsigned dp_uint2v __attribute__((ext_vector_type(2)));
-// v_permlane32_swap: lanes 32..63 of a <-> lanes 0..31 of b; the sum then holds a's lane-pair sums in lanes 0..31 and b's in
-// lanes 32..63
-__device__ __forceinline__ float dp_swap32_add(float a, float b) {
-  const dp_uint2v r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-  // NB: element access as r[0]/r[1] + __uint_as_float; `bit_cast(float, r.x) + bit_cast(float, r.y)` is miscompiled
-  // by hipcc 7.2 into x + x (checked in the ISA of gs_render_bwd_wave.hip)
-  const unsigned x = r[0], y = r[1];
-  return __uint_as_float(x) + __uint_as_float(y);
-}
-// v_permlane16_swap: odd rows of a <-> even rows of b; with a = (u | w), b = (x | y) as produced by dp_swap32_add the sum
-// holds u, x, w, y in rows 0..3 (16 lanes each)
-__device__ __forceinline__ float dp_swap16_add(float a, float b) {
-  const dp_uint2v r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
-  const unsigned x = r[0], y = r[1];  // (same note)
-  return __uint_as_float(x) + __uint_as_float(y);
-}
-// inclusive scan inside each row of 16 lanes: lane 15 of every row ends with the row total
-__device__ __forceinline__ float dp_row_total_in_lane15(float v) {
-  v += dp_dppw<0x111, 0xf, true>(v);  // row_shr:1
-  v += dp_dppw<0x112, 0xf, true>(v);  // row_shr:2
-  v += dp_dppw<0x114, 0xf, true>(v);  // row_shr:4
-  v += dp_dppw<0x118, 0xf, true>(v);  // row_shr:8
-  return v;
-}
-// the same scan in the other direction: lane 0 of every row ends with the row total
-__device__ __forceinline__ float dp_row_total_in_lane0(float v) {
-  v += dp_dppw<0x101, 0xf, true>(v);  // row_shl:1
-  v += dp_dppw<0x102, 0xf, true>(v);  // row_shl:2
-  v += dp_dppw<0x104, 0xf, true>(v);  // row_shl:4
-  v += dp_dppw<0x108, 0xf, true>(v);  // row_shl:8
-  return v;
-}
-
 // GRAD_MEANS: the six sums the mean gradient needs (mean2D x, y; conic xx, xy, yy; depth) go to the Gaussian's float64 row in
 // ONE atomic instruction of six lanes, seven with GRAD_OPACITY (the general kernel's has twelve).
 // GRAD_OPACITY alone: one sum, a fixed reduction tree, one lane's atomic.
@@ -353,17 +314,17 @@ __global__ void __launch_bounds__(64, 4) depth_bwd_wave_kernel(
         }
       }
       if (GRAD_MEANS) {
-        const float s0 = dp_swap32_add(v_mx, v_cxx), s1 = dp_swap32_add(v_my, v_cxy);  // (mx|cxx) (my|cxy)
-        const float s2 = dp_swap32_add(v_cyy, v_id);                                   // (cyy|id)
-        const float s3 = GRAD_OPACITY ? dp_swap32_add(v_op, 0.f) : 0.f;                // (op|-)
-        const float t0 = dp_row_total_in_lane15(dp_swap16_add(s0, s1));                // rows: mx my cxx cxy   (lane 15)
-        const float t1 = dp_row_total_in_lane0(dp_swap16_add(s2, s3));                 // rows: cyy op id -     (lane 0)
+        const float s0 = swap32_add(v_mx, v_cxx), s1 = swap32_add(v_my, v_cxy);  // (mx|cxx) (my|cxy)
+        const float s2 = swap32_add(v_cyy, v_id);                                   // (cyy|id)
+        const float s3 = GRAD_OPACITY ? swap32_add(v_op, 0.f) : 0.f;                // (op|-)
+        const float t0 = row_total_in_lane15(swap16_add(s0, s1));                // rows: mx my cxx cxy   (lane 15)
+        const float t1 = row_total_in_lane0(swap16_add(s2, s3));                 // rows: cyy op id -     (lane 0)
         const float tot = (lr == 15 ? t0 : t1) * lane_scale;
         // one global_atomic_add_f64 instruction, seven (six) lanes, one 128-byte line
         if (lane_adds) atomicAdd(grad_rows + (size_t)s_id[j] * GR_STRIDE + lane_slot, (double)tot);
       } else {
         // the four row totals (lane 15 of each row), added in a fixed order; one lane's atomic
-        const float t = dp_row_total_in_lane15(v_op);
+        const float t = row_total_in_lane15(v_op);
         const int ti = __builtin_bit_cast(int, t);
         const float r0 = __int_as_float(__builtin_amdgcn_readlane(ti, 15)), r1 = __int_as_float(__builtin_amdgcn_readlane(ti, 31));
         const float r2 = __int_as_float(__builtin_amdgcn_readlane(ti, 47)), r3 = __int_as_float(__builtin_amdgcn_readlane(ti, 63));

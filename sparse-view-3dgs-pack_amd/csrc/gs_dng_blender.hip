@@ -29,6 +29,8 @@
 //   commute: the value does not depend on their order.  (A counting workgroup that walks all P rows alone needs no memset but
 //   is the launch's long pole - with the SH colours to evaluate it is slower than torch's own statements.)
 #include "gs_common.h"
+#include "gs_launch.h"
+#include "gs_reduce.h"
 
 namespace {
 
@@ -40,16 +42,6 @@ namespace {
 #define BL_LDS_STRIDE (3 * BL_MAX_COEF + 1)  // odd: a lane's row starts in its own bank
 
 static_assert(BL_MAX_BLOCKS <= GS_BLOCK, "the partial counts fit one workgroup's LDS array");
-
-// sum over the workgroup, fixed tree; element 0 holds the result
-__device__ __forceinline__ void bl_block_count(int v, int* sh, int t) {
-  sh[t] = v;
-  __syncthreads();
-  for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
-}
 
 __device__ __forceinline__ bool bl_white(float r, float g, float b, float thr) {
   // torch's min over the channels hands a NaN on; a NaN does not pass the comparison
@@ -75,14 +67,16 @@ __global__ __launch_bounds__(GS_BLOCK) void bt_mask_kernel(const float* gt, cons
       masked += m ? 1 : 0;
     }
   }
-  bl_block_count(masked, sh, t);
+  sh[t] = masked;
+  gs_block_tree<GS_BLOCK, 1>(sh, t);
   if (t == 0) part[blockIdx.x] = sh[0];
 }
 
 __global__ __launch_bounds__(GS_BLOCK) void bt_count_kernel(const int32_t* part, int nblocks, int32_t* count) {
   __shared__ int sh[GS_BLOCK];
   const int t = threadIdx.x;
-  bl_block_count(t < nblocks ? part[t] : 0, sh, t);
+  sh[t] = t < nblocks ? part[t] : 0;
+  gs_block_tree<GS_BLOCK, 1>(sh, t);
   if (t == 0) count[0] = sh[0];
 }
 
@@ -95,7 +89,8 @@ __device__ __forceinline__ float wr_opacity(float o, float factor) {
 
 // the workgroup's count of firing rows, then ONE integer add into the count the entry has zeroed on the stream
 __device__ __forceinline__ void wr_count(bool fires, int* sh, int t, int32_t* counts) {
-  bl_block_count(fires ? 1 : 0, sh, t);
+  sh[t] = fires ? 1 : 0;
+  gs_block_tree<GS_BLOCK, 1>(sh, t);
   if (t == 0 && sh[0] != 0) atomicAdd(counts, sh[0]);
 }
 
@@ -210,18 +205,13 @@ __global__ __launch_bounds__(GS_BLOCK) void wr_sh_kernel(const float* xyz, ShRow
 
 static bool bl_n_ok(int64_t n) { return n >= 1 && n < BL_MAX_N; }
 
-static int bl_blocks(size_t n) {
-  size_t b = (n + BL_BLOCK_ELEMS - 1) / BL_BLOCK_ELEMS;
-  return (int)(b > BL_MAX_BLOCKS ? BL_MAX_BLOCKS : b);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t gs_blender_tmp_bytes(int64_t n) {
   if (!bl_n_ok(n)) return 0;
-  return gs_align((size_t)bl_blocks((size_t)n) * sizeof(int32_t));
+  return gs_align((size_t)gs_capped_blocks((size_t)n, BL_BLOCK_ELEMS, BL_MAX_BLOCKS) * sizeof(int32_t));
 }
 
 int gs_blender_target(const float* gt, const float* mono, int32_t H, int32_t W, float thr, void* tmp, uint8_t* mask, int32_t* count,
@@ -229,7 +219,7 @@ int gs_blender_target(const float* gt, const float* mono, int32_t H, int32_t W, 
   if (H < 1 || W < 1 || !bl_n_ok((int64_t)H * (int64_t)W)) return GS_E_SHAPE;
   if (!gt || !tmp || !mask || !count || (target && !mono)) return GS_E_NULL;
   const size_t n = (size_t)H * (size_t)W;
-  const int nb = bl_blocks(n);
+  const int nb = gs_capped_blocks(n, BL_BLOCK_ELEMS, BL_MAX_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(bt_mask_kernel, dim3(nb), dim3(GS_BLOCK), 0, s, gt, mono, n, thr, nb, mask, target, (int32_t*)tmp);
   GS_LAUNCH_CHECK(s, 0);

@@ -29,6 +29,8 @@
 //   rule resets, the raw opacity becomes `value`.  Black before white.  The colours are not written, so the LAST workgroup of the
 //   grid edits nothing and counts the rows of both rules over all P instead (integer LDS tree) - counts[2] = black, white.
 #include "gs_common.h"
+#include "gs_launch.h"
+#include "gs_reduce.h"
 
 namespace {
 
@@ -71,26 +73,8 @@ __global__ __launch_bounds__(DT_MASK_THREADS) void dtu_mask_kernel(const float* 
     }
   }
   sh[t] = masked;
-  __syncthreads();
-  for (int w = DT_MASK_THREADS / 2; w > 0; w >>= 1) {
-    if (t < w) sh[t] += sh[t + w];
-    __syncthreads();
-  }
+  gs_block_tree<DT_MASK_THREADS, 1>(sh, t);
   if (t == 0) count[0] = sh[0];
-}
-
-// sum over the workgroup, fixed tree; element 0 holds the result
-__device__ __forceinline__ void ms_block_sum(double v, unsigned long long n, double* sh, unsigned long long* shn, int t) {
-  sh[t] = v;
-  shn[t] = n;
-  __syncthreads();
-  for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      sh[t] += sh[t + w];
-      shn[t] += shn[t + w];
-    }
-    __syncthreads();
-  }
 }
 
 // mode 0: x over mask == 0;  mode 1: x^2 (in float64) over mask != 0
@@ -114,7 +98,9 @@ __global__ __launch_bounds__(GS_BLOCK) void ms_stats_kernel(const float* x, cons
       }
     }
   }
-  ms_block_sum(v, cnt, sh, shn, t);
+  sh[t] = v;
+  shn[t] = cnt;
+  gs_block_tree<GS_BLOCK, 1, 1>(sh, t, shn);
   if (t == 0) {
     MsPartial p;
     p.s = sh[0]; p.n = shn[0];
@@ -122,7 +108,9 @@ __global__ __launch_bounds__(GS_BLOCK) void ms_stats_kernel(const float* x, cons
   }
 }
 
-// the partials in index order, by lane 0, from LDS -> (sum, count) in sh_s[0], sh_n[0] for every lane of the workgroup
+// the partials in index order, by lane 0, from LDS -> (sum, count) in sh_s[0], sh_n[0] for every lane of the workgroup.  EVERY
+// workgroup of mf_fill_kernel forms the mean this way and all must get the same bits; the serial index order is what the fill's
+// parity records hold, so it is NOT gs_reduce.h's tree and stays here on purpose.
 __device__ __forceinline__ void ms_total(const MsPartial* part, int nblocks, double* sh_s, unsigned long long* sh_n, int t) {
   for (int i = t; i < nblocks; i += GS_BLOCK) {
     sh_s[i] = part[i].s;
@@ -212,11 +200,7 @@ __global__ __launch_bounds__(GS_BLOCK) void cr_kernel(const float* colour, float
       nw += fw ? 1 : 0;
     }
     sh[t] = nb; sh[GS_BLOCK + t] = nw;
-    __syncthreads();
-    for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-      if (t < w) { sh[t] += sh[t + w]; sh[GS_BLOCK + t] += sh[GS_BLOCK + t + w]; }
-      __syncthreads();
-    }
+    gs_block_tree<GS_BLOCK, 2>(sh, t);
     if (t == 0) { counts[0] = sh[0]; counts[1] = sh[GS_BLOCK]; }
     return;
   }
@@ -234,11 +218,6 @@ __global__ __launch_bounds__(GS_BLOCK) void cr_kernel(const float* colour, float
 }
 
 static bool dt_n_ok(int64_t n) { return n >= 1 && n < DT_MAX_N; }
-
-static int dt_blocks(size_t n) {
-  size_t b = (n + DT_BLOCK_ELEMS - 1) / DT_BLOCK_ELEMS;
-  return (int)(b > DT_MAX_BLOCKS ? DT_MAX_BLOCKS : b);
-}
 
 static unsigned dt_grid(size_t n) { return (unsigned)((n + DT_BLOCK_ELEMS - 1) / DT_BLOCK_ELEMS); }
 
@@ -260,13 +239,13 @@ int gs_dtu_mask(const float* gt, int32_t H, int32_t W, float thr, int32_t run, u
 
 size_t gs_masked_tmp_bytes(int64_t n) {
   if (!dt_n_ok(n)) return 0;
-  return gs_align(sizeof(MsRecord)) + gs_align((size_t)dt_blocks((size_t)n) * sizeof(MsPartial));
+  return gs_align(sizeof(MsRecord)) + gs_align((size_t)gs_capped_blocks((size_t)n, DT_BLOCK_ELEMS, DT_MAX_BLOCKS) * sizeof(MsPartial));
 }
 
 int gs_masked_fill_fwd(const float* x, const uint8_t* mask, int64_t n, void* tmp, float* out, float* mean_out, void* stream) {
   if (!dt_n_ok(n)) return GS_E_SHAPE;
   if (!x || !mask || !tmp || !out) return GS_E_NULL;
-  const int nb = dt_blocks((size_t)n);
+  const int nb = gs_capped_blocks((size_t)n, DT_BLOCK_ELEMS, DT_MAX_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ms_stats_kernel, dim3(nb), dim3(GS_BLOCK), 0, s, x, mask, (size_t)n, 0, nb, dt_partials(tmp));
   GS_LAUNCH_CHECK(s, 0);
@@ -288,7 +267,7 @@ int gs_masked_fill_bwd(const float* g, const uint8_t* mask, int64_t n, float* g_
 int gs_alpha_penalty_fwd(const float* alpha, const uint8_t* mask, int64_t n, void* tmp, float* out, void* stream) {
   if (!dt_n_ok(n)) return GS_E_SHAPE;
   if (!alpha || !mask || !tmp || !out) return GS_E_NULL;
-  const int nb = dt_blocks((size_t)n);
+  const int nb = gs_capped_blocks((size_t)n, DT_BLOCK_ELEMS, DT_MAX_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ms_stats_kernel, dim3(nb), dim3(GS_BLOCK), 0, s, alpha, mask, (size_t)n, 1, nb, dt_partials(tmp));
   GS_LAUNCH_CHECK(s, 0);

@@ -26,6 +26,8 @@
 // No atomics, no read-back, no host synchronisation: two runs give the same bits.
 #include "gs_common.h"
 #include "gs_dng_reg_act.h"
+#include "gs_launch.h"
+#include "gs_reduce.h"
 
 namespace {
 
@@ -57,14 +59,12 @@ struct DrArgs {
   DrPartial* part;  // [nblocks]
 };
 
-__device__ __forceinline__ void unpack4(const float4 q, float* v) { v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
-
 // rows [i, i + 4) of a [P,3] array (i a multiple of 4) -> v[12]; rows at or beyond P are left alone
 __device__ __forceinline__ void load_rows3(const float* p, size_t i, size_t P, int vec, float (&v)[12]) {
   if (vec && i + 4 <= P) {
     const float4* q = reinterpret_cast<const float4*>(p + 3 * i);
     const float4 a = q[0], b = q[1], c = q[2];
-    unpack4(a, v); unpack4(b, v + 4); unpack4(c, v + 8);
+    gs_unpack4(a, v); gs_unpack4(b, v + 4); gs_unpack4(c, v + 8);
   } else {
     for (int k = 0; k < 4; k++)
       if (i + k < P)
@@ -82,24 +82,6 @@ __device__ __forceinline__ void store_rows3(float* p, size_t i, size_t P, int ve
     for (int k = 0; k < 4; k++)
       if (i + k < P)
         for (int c = 0; c < 3; c++) p[3 * (i + k) + c] = v[3 * k + c];
-  }
-}
-
-__device__ __forceinline__ void load_rows1(const float* p, size_t i, size_t P, int vec, float (&v)[4]) {
-  if (vec && i + 4 <= P) {
-    unpack4(*reinterpret_cast<const float4*>(p + i), v);
-  } else {
-    for (int k = 0; k < 4; k++)
-      if (i + k < P) v[k] = p[i + k];
-  }
-}
-
-__device__ __forceinline__ void store_rows1(float* p, size_t i, size_t P, int vec, const float (&v)[4]) {
-  if (vec && i + 4 <= P) {
-    *reinterpret_cast<float4*>(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int k = 0; k < 4; k++)
-      if (i + k < P) p[i + k] = v[k];
   }
 }
 
@@ -131,21 +113,6 @@ __device__ __forceinline__ void dr_opacity(float v, int raw, float& o, float& om
   }
 }
 
-// sum over the workgroup, fixed tree; element 0 of each row of sh / shn holds the result
-__device__ __forceinline__ void dr_block_sum(const double (&v)[DR_Q], const unsigned long long (&n)[2], double* sh,
-                                             unsigned long long* shn, int t) {
-  for (int q = 0; q < DR_Q; q++) sh[q * GS_BLOCK + t] = v[q];
-  shn[t] = n[0]; shn[GS_BLOCK + t] = n[1];
-  __syncthreads();
-  for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w) {
-      for (int q = 0; q < DR_Q; q++) sh[q * GS_BLOCK + t] += sh[q * GS_BLOCK + t + w];
-      shn[t] += shn[t + w]; shn[GS_BLOCK + t] += shn[GS_BLOCK + t + w];
-    }
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(GS_BLOCK) void dr_stats_kernel(DrArgs a) {
   __shared__ double sh[DR_Q * GS_BLOCK];
   __shared__ unsigned long long shn[2 * GS_BLOCK];
@@ -157,7 +124,7 @@ __global__ __launch_bounds__(GS_BLOCK) void dr_stats_kernel(DrArgs a) {
     if (i >= a.P) continue;
     float s[12] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f}, ov[4] = {0.f, 0.f, 0.f, 0.f};
     load_rows3(a.scaling, i, a.P, a.vec_s, s);
-    load_rows1(a.opacity, i, a.P, a.vec_o, ov);
+    gs_load4(a.opacity, i, a.P, a.vec_o, ov);
     for (int k = 0; k < DR_ROWS; k++) {
       if (i + k >= a.P) break;
       const DrRow r = dr_row(s + 3 * k, a.raw);
@@ -175,7 +142,9 @@ __global__ __launch_bounds__(GS_BLOCK) void dr_stats_kernel(DrArgs a) {
       }
     }
   }
-  dr_block_sum(v, n, sh, shn, t);
+  gs_rows_put<GS_BLOCK>(v, sh, t);
+  gs_rows_put<GS_BLOCK>(n, shn, t);
+  gs_block_tree<GS_BLOCK, DR_Q, 2>(sh, t, shn);
   if (t == 0) {
     DrPartial p;
     for (int q = 0; q < DR_Q; q++) p.s[q] = sh[q * GS_BLOCK];
@@ -190,11 +159,13 @@ __global__ __launch_bounds__(GS_BLOCK) void dr_finish_kernel(DrArgs a, float* ou
   const int t = threadIdx.x;
   double v[DR_Q] = {0.0, 0.0, 0.0, 0.0};
   unsigned long long n[2] = {0ull, 0ull};
-  for (int i = t; i < a.nblocks; i += GS_BLOCK) {
+  for (int i = t; i < a.nblocks; i += GS_BLOCK) {  // (a partial is a record of two types: not gs_partials_tree_sum's [count][N])
     for (int q = 0; q < DR_Q; q++) v[q] += a.part[i].s[q];
     n[0] += a.part[i].n[0]; n[1] += a.part[i].n[1];
   }
-  dr_block_sum(v, n, sh, shn, t);
+  gs_rows_put<GS_BLOCK>(v, sh, t);
+  gs_rows_put<GS_BLOCK>(n, shn, t);
+  gs_block_tree<GS_BLOCK, DR_Q, 2>(sh, t, shn);
   if (t != 0) return;
   const double P = (double)a.P, n_hi = (double)shn[0], n_lo = (double)shn[GS_BLOCK];
   const double shape = sh[0] / P, scale = sh[GS_BLOCK] / P;
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(GS_BLOCK) void dr_bwd_kernel(DrArgs a, const float*
   }
   if (g_opacity) {
     float ov[4] = {0.f, 0.f, 0.f, 0.f}, go[4];
-    load_rows1(a.opacity, i, a.P, a.vec_o, ov);
+    gs_load4(a.opacity, i, a.P, a.vec_o, ov);
     const double k_hi = -2.0 * c[2] / (double)rec->n_hi, k_lo = -2.0 * c[2] / (double)rec->n_lo;  // used by members only
     for (int k = 0; k < DR_ROWS; k++) {
       float o, om;
@@ -250,7 +221,7 @@ __global__ __launch_bounds__(GS_BLOCK) void dr_bwd_kernel(DrArgs a, const float*
       if (a.raw) g *= (double)o * (double)om;  // do / draw = o (1 - o)
       go[k] = (float)g;
     }
-    store_rows1(g_opacity, i, a.P, a.vec_o, go);
+    gs_store4(g_opacity, i, a.P, a.vec_o, go);
   }
 }
 
@@ -345,16 +316,7 @@ __global__ __launch_bounds__(GS_BLOCK) void nm_kernel(const float* xyz, size_t P
 }
 
 // ---- host side ----
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static bool dr_p_ok(int64_t P) { return P >= 1 && P <= DR_MAX_P; }
-
-static int dr_blocks(size_t P, int max_blocks) {
-  size_t b = (P + GS_DNG_REG_BLOCK_ROWS - 1) / GS_DNG_REG_BLOCK_ROWS;
-  if (b > GS_DNG_REG_MAX_BLOCKS) b = GS_DNG_REG_MAX_BLOCKS;
-  if (max_blocks > 0 && b > (size_t)max_blocks) b = (size_t)max_blocks;
-  return (int)b;
-}
 
 static unsigned row_grid(size_t P) {  // one lane per four rows
   const size_t lanes = (P + DR_ROWS - 1) / DR_ROWS;
@@ -365,7 +327,7 @@ static DrArgs dr_args(const float* scaling, const float* opacity, int64_t P, int
   DrArgs a = {};
   a.scaling = scaling; a.opacity = opacity; a.P = (size_t)P;
   a.raw = (flags & GS_DNG_REG_RAW) != 0;
-  a.vec_s = aligned16(scaling); a.vec_o = aligned16(opacity);
+  a.vec_s = gs_aligned16(scaling); a.vec_o = gs_aligned16(opacity);
   a.rec = (DrRecord*)tmp;
   a.part = (DrPartial*)((char*)tmp + gs_align(sizeof(DrRecord)));
   return a;
@@ -377,7 +339,7 @@ extern "C" {
 
 size_t gs_dng_reg_tmp_bytes(int64_t P) {
   if (!dr_p_ok(P)) return 0;
-  return gs_align(sizeof(DrRecord)) + gs_align((size_t)dr_blocks((size_t)P, 0) * sizeof(DrPartial));
+  return gs_align(sizeof(DrRecord)) + gs_align((size_t)gs_capped_blocks((size_t)P, GS_DNG_REG_BLOCK_ROWS, GS_DNG_REG_MAX_BLOCKS) * sizeof(DrPartial));
 }
 
 int gs_dng_reg_fwd(const float* scaling, const float* opacity, int64_t P, double w_shape, double w_scale, double w_opa,
@@ -385,7 +347,7 @@ int gs_dng_reg_fwd(const float* scaling, const float* opacity, int64_t P, double
   if (!dr_p_ok(P) || max_blocks < 0 || (flags & ~GS_DNG_REG_RAW)) return GS_E_SHAPE;
   if (!scaling || !opacity || !tmp || !out) return GS_E_NULL;
   DrArgs a = dr_args(scaling, opacity, P, flags, tmp);
-  a.nblocks = dr_blocks(a.P, max_blocks);
+  a.nblocks = gs_capped_blocks(a.P, GS_DNG_REG_BLOCK_ROWS, GS_DNG_REG_MAX_BLOCKS, max_blocks);
   a.w[0] = w_shape; a.w[1] = w_scale; a.w[2] = w_opa;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(dr_stats_kernel, dim3(a.nblocks), dim3(GS_BLOCK), 0, s, a);
@@ -401,8 +363,8 @@ int gs_dng_reg_bwd(const float* scaling, const float* opacity, int64_t P, int32_
   if (!tmp || (!g_terms && !g_total) || (!g_scaling && !g_opacity) || (g_scaling && !scaling) || (g_opacity && !opacity))
     return GS_E_NULL;
   DrArgs a = dr_args(scaling, opacity, P, flags, (void*)tmp);
-  a.vec_s = a.vec_s && aligned16(g_scaling);
-  a.vec_o = a.vec_o && aligned16(g_opacity);
+  a.vec_s = a.vec_s && gs_aligned16(g_scaling);
+  a.vec_o = a.vec_o && gs_aligned16(g_opacity);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(dr_bwd_kernel, dim3(row_grid(a.P)), dim3(GS_BLOCK), 0, s, a, g_terms, g_total, g_scaling, g_opacity);
   GS_LAUNCH_CHECK(s, 0);
@@ -414,7 +376,7 @@ int gs_view_dirs_fwd(const float* xyz, const float* campos, int64_t P, float* ou
   if (!xyz || !campos || !out) return GS_E_NULL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(vd_fwd_kernel, dim3(row_grid((size_t)P)), dim3(GS_BLOCK), 0, s, xyz, campos, (size_t)P,
-                     (int)(aligned16(xyz) && aligned16(out)), out);
+                     (int)(gs_aligned16(xyz) && gs_aligned16(out)), out);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
 }
@@ -424,7 +386,7 @@ int gs_view_dirs_bwd(const float* xyz, const float* campos, int64_t P, const flo
   if (!xyz || !campos || !g || !g_xyz) return GS_E_NULL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(vd_bwd_kernel, dim3(row_grid((size_t)P)), dim3(GS_BLOCK), 0, s, xyz, campos, (size_t)P,
-                     (int)(aligned16(xyz) && aligned16(g) && aligned16(g_xyz)), g, g_xyz);
+                     (int)(gs_aligned16(xyz) && gs_aligned16(g) && gs_aligned16(g_xyz)), g, g_xyz);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
 }
@@ -434,7 +396,7 @@ int gs_near_mask(const float* xyz, int64_t P, const float* centers, int32_t K, f
   if (!xyz || !centers || !mask) return GS_E_NULL;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(nm_kernel, dim3(row_grid((size_t)P)), dim3(GS_BLOCK), 0, s, xyz, (size_t)P, centers, (int)K, near,
-                     (int)aligned16(xyz), (int)(((uintptr_t)mask & 3) == 0), mask);
+                     (int)gs_aligned16(xyz), (int)(((uintptr_t)mask & 3) == 0), mask);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;
 }

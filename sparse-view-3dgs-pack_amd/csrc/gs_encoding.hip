@@ -16,6 +16,7 @@
 //               2 x 256 entries plus one chunk sum per 256 entries.  Every slot is written, zero where nothing landed.
 // Grid backward to the inputs: one thread per (point, dim) sums dy_dx[b, l, d, c] * grad[b, l, c] over (l, c) in order.
 #include "gs_common.h"
+#include "gs_reduce.h"
 
 #include <cmath>
 
@@ -267,13 +268,7 @@ __global__ void __launch_bounds__(GS_BLOCK) grid_gather_kernel(const float* __re
     for (int c = 0; c < C; c++) contrib[(size_t)i * C + c] = v[c];
 #pragma unroll
   for (int c = 0; c < C; c++) s_sum[c][threadIdx.x] = v[c];
-  __syncthreads();
-  for (int h = GS_BLOCK / 2; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h)
-#pragma unroll
-      for (int c = 0; c < C; c++) s_sum[c][threadIdx.x] += s_sum[c][threadIdx.x + h];
-    __syncthreads();
-  }
+  gs_block_tree<GS_BLOCK, C>(&s_sum[0][0], (int)threadIdx.x);
   if (threadIdx.x < C) chunk[(size_t)blockIdx.x * C + threadIdx.x] = s_sum[threadIdx.x][0];
 }
 

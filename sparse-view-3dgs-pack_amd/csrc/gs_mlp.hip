@@ -24,6 +24,7 @@
 //   wave).  At the end every workgroup writes its partial [15616] to tmp; hd_reduce_kernel adds the partials in workgroup
 //   order.  No atomics: the same inputs give the same bits.  ReLU'(0) = 0.
 #include "gs_common.h"
+#include "gs_launch.h"
 
 namespace {
 
@@ -398,17 +399,6 @@ __global__ __launch_bounds__(GS_BLOCK) void hd_reduce_kernel(const float* part, 
 #define HD_MAX_ROWS ((int64_t)1 << 40)
 
 static int64_t hd_tiles(int64_t B) { return (B + GS_DNG_HEADS_TILE_ROWS - 1) / GS_DNG_HEADS_TILE_ROWS; }
-static int hd_blocks(int64_t B) {
-  const int64_t t = hd_tiles(B);
-  return (int)(t < GS_DNG_HEADS_MAX_BLOCKS ? t : GS_DNG_HEADS_MAX_BLOCKS);
-}
-// a grid of at most `dflt` workgroups, or of at most max_blocks where the caller caps it (0: no cap)
-static int hd_grid(int64_t tiles, int64_t dflt, int32_t max_blocks) {
-  int64_t g = tiles < dflt ? tiles : dflt;
-  if (max_blocks > 0 && g > max_blocks) g = max_blocks;
-  return (int)g;
-}
-static bool hd_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -416,7 +406,7 @@ extern "C" {
 
 size_t gs_dng_heads_tmp_bytes(int64_t B) {
   if (B <= 0 || B > HD_MAX_ROWS) return 0;
-  return gs_align((size_t)hd_blocks(B) * G_END * sizeof(float));
+  return gs_align((size_t)gs_capped_blocks((size_t)B, GS_DNG_HEADS_TILE_ROWS, GS_DNG_HEADS_MAX_BLOCKS) * G_END * sizeof(float));
 }
 
 int gs_dng_heads_fwd(const float* enc_x, const float* enc_d, int64_t B, const float* w_s0, const float* w_s1, const float* w_s2,
@@ -430,11 +420,11 @@ int gs_dng_heads_fwd(const float* enc_x, const float* enc_d, int64_t B, const fl
   a.enc_x = enc_x; a.enc_d = enc_d; a.B = B; a.ntiles = hd_tiles(B);
   a.w[0] = w_s0; a.w[1] = w_s1; a.w[2] = w_s2; a.w[3] = w_c0; a.w[4] = w_c1;
   a.sigma = sigma; a.color = color;
-  a.vec = hd_aligned(enc_x) && hd_aligned(enc_d);
+  a.vec = gs_aligned16(enc_x) && gs_aligned16(enc_d);
   hipStream_t s = (hipStream_t)stream;
   // one workgroup per CU for the colour form (370 registers: one wave per SIMD, so a second workgroup would only reload the
   // weights); the sigma-only form runs two waves per SIMD and its 62 KB of LDS fit twice: two workgroups per CU
-  const dim3 grid((unsigned)hd_grid(a.ntiles, (col ? 1 : 2) * (int64_t)GS_DNG_HEADS_MAX_BLOCKS, max_blocks));
+  const dim3 grid((unsigned)gs_capped_blocks((size_t)a.ntiles, 1, (col ? 1 : 2) * (size_t)GS_DNG_HEADS_MAX_BLOCKS, max_blocks));
   if (col) hipLaunchKernelGGL(hd_fwd_kernel<true>, grid, dim3(GS_BLOCK), 0, s, a);
   else hipLaunchKernelGGL(hd_fwd_kernel<false>, grid, dim3(GS_BLOCK), 0, s, a);
   GS_LAUNCH_CHECK(s, 0);
@@ -476,8 +466,8 @@ int gs_dng_heads_bwd(const float* enc_x, const float* enc_d, int64_t B, const fl
   a.g_sigma = g_sigma; a.g_color = col ? g_color : nullptr;
   a.g_enc_x = g_enc_x; a.g_enc_d = col ? g_enc_d : nullptr;
   a.part = want_w ? (float*)tmp : nullptr;
-  a.vec = hd_aligned(enc_x) && hd_aligned(enc_d) && hd_aligned(g_enc_x) && hd_aligned(g_enc_d);
-  const int nb = hd_grid(a.ntiles, GS_DNG_HEADS_MAX_BLOCKS, max_blocks);
+  a.vec = gs_aligned16(enc_x) && gs_aligned16(enc_d) && gs_aligned16(g_enc_x) && gs_aligned16(g_enc_d);
+  const int nb = gs_capped_blocks((size_t)a.ntiles, 1, GS_DNG_HEADS_MAX_BLOCKS, max_blocks);
   if (col) hipLaunchKernelGGL(hd_bwd_kernel<true>, dim3(nb), dim3(GS_BLOCK), 0, s, a);
   else hipLaunchKernelGGL(hd_bwd_kernel<false>, dim3(nb), dim3(GS_BLOCK), 0, s, a);
   GS_LAUNCH_CHECK(s, 0);

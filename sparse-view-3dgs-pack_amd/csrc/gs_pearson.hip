@@ -20,6 +20,8 @@
 //   A NaN r (constant sequence) gives zero gradients.
 // No atomics, no read-back, no host synchronisation: two runs give the same bits.
 #include "gs_common.h"
+#include "gs_launch.h"
+#include "gs_reduce.h"
 
 namespace {
 
@@ -48,38 +50,10 @@ struct PrArgs {
   double* part;   // [nblocks][PR_Q]
 };
 
-static int pr_blocks(size_t n) {
-  const size_t b = (n + GS_PEARSON_BLOCK_ELEMS - 1) / GS_PEARSON_BLOCK_ELEMS;
-  return (int)(b < GS_PEARSON_MAX_BLOCKS ? b : GS_PEARSON_MAX_BLOCKS);
-}
-
 __device__ __forceinline__ float pr_form(float t, int form) {
   if (form == GS_PEARSON_NEG) return -t;
   if (form == GS_PEARSON_RECIP200) return 1.f / (t + 200.f);
   return t;
-}
-
-// elements [i, i + 4) of p (i a multiple of 4) -> v; the ones at or beyond n are left alone
-__device__ __forceinline__ void pr_load4(const float* p, size_t i, size_t n, int vec, float (&v)[4]) {
-  if (vec && i + 4 <= n) {
-    const float4 q = *reinterpret_cast<const float4*>(p + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    for (int k = 0; k < 4; k++)
-      if (i + k < n) v[k] = p[i + k];
-  }
-}
-
-// sum over the workgroup, fixed tree; lane 0's v holds the result.  sh: [PR_Q][GS_BLOCK]
-__device__ __forceinline__ void pr_block_sum(double (&v)[PR_Q], double* sh, int t) {
-  for (int q = 0; q < PR_Q; q++) sh[q * GS_BLOCK + t] = v[q];
-  __syncthreads();
-  for (int w = GS_BLOCK / 2; w > 0; w >>= 1) {
-    if (t < w)
-      for (int q = 0; q < PR_Q; q++) sh[q * GS_BLOCK + t] += sh[q * GS_BLOCK + t + w];
-    __syncthreads();
-  }
-  for (int q = 0; q < PR_Q; q++) v[q] = sh[q * GS_BLOCK];
 }
 
 __global__ __launch_bounds__(GS_BLOCK) void pr_stats_kernel(PrArgs a) {
@@ -94,8 +68,8 @@ __global__ __launch_bounds__(GS_BLOCK) void pr_stats_kernel(PrArgs a) {
     float xv[PR_ITEMS][4], tv[PR_ITEMS][4];
     for (int j = 0; j < PR_ITEMS; j++) {
       const size_t i = base + 4 * ((size_t)j * GS_BLOCK + t);
-      pr_load4(a.x, i, a.n, a.vec, xv[j]);
-      pr_load4(a.t, i, a.n, a.vec, tv[j]);
+      gs_load4(a.x, i, a.n, a.vec, xv[j]);
+      gs_load4(a.t, i, a.n, a.vec, tv[j]);
     }
     for (int j = 0; j < PR_ITEMS; j++) {
       const size_t i = base + 4 * ((size_t)j * GS_BLOCK + t);
@@ -112,17 +86,15 @@ __global__ __launch_bounds__(GS_BLOCK) void pr_stats_kernel(PrArgs a) {
       }
     }
   }
-  pr_block_sum(v, sh, t);
-  if (t < PR_Q) a.part[(size_t)blockIdx.x * PR_Q + t] = sh[t * GS_BLOCK];
+  gs_block_tree_sum<GS_BLOCK>(v, sh, t);
+  if (t < PR_Q) a.part[(size_t)blockIdx.x * PR_Q + t] = sh[t * GS_BLOCK];  // (lane t < PR_Q takes row t's result)
 }
 
 __global__ __launch_bounds__(GS_BLOCK) void pr_finish_kernel(PrArgs a, float* out, int32_t* branch_out) {
   __shared__ double sh[PR_Q * GS_BLOCK];
   const int t = threadIdx.x;
-  double v[PR_Q] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = t; i < a.nblocks; i += GS_BLOCK)
-    for (int q = 0; q < PR_Q; q++) v[q] += a.part[(size_t)i * PR_Q + q];
-  pr_block_sum(v, sh, t);
+  double v[PR_Q];
+  gs_partials_tree_sum<GS_BLOCK>(a.part, a.nblocks, v, sh, t);
   if (t != 0) return;
   PrStats s;
   const double n = (double)a.n;
@@ -175,8 +147,8 @@ __global__ __launch_bounds__(GS_BLOCK) void pr_bwd_kernel(PrArgs a, const float*
   const double mx = (double)s->x0 + s->mdx, my = (double)s->y0[b] + s->mdy[b];
   const double dy_dt = form == GS_PEARSON_NEG ? -1.0 : 1.0;
   float xv[4] = {0.f, 0.f, 0.f, 0.f}, tv[4] = {0.f, 0.f, 0.f, 0.f}, gx[4], gt[4];
-  pr_load4(a.x, i, a.n, a.vec, xv);
-  pr_load4(a.t, i, a.n, a.vec, tv);
+  gs_load4(a.x, i, a.n, a.vec, xv);
+  gs_load4(a.t, i, a.n, a.vec, tv);
   for (int k = 0; k < 4; k++) {
     const double xc = (double)xv[k] - mx, yc = (double)pr_form(tv[k], form) - my;
     gx[k] = ok ? (float)(up * (yc * inv - r * xc / Sxx)) : 0.f;
@@ -201,14 +173,12 @@ static int pr_check(int64_t n, int form_a, int form_b) {
   return GS_OK;
 }
 
-static bool pr_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 static PrArgs pr_args(const float* x, const float* t, int64_t n, int form_a, int form_b, void* tmp) {
   PrArgs a = {};
   a.x = x; a.t = t; a.n = (size_t)n;
   a.form[0] = form_a; a.form[1] = form_b;
-  a.vec = pr_aligned(x) && pr_aligned(t);
-  a.nblocks = pr_blocks(a.n);
+  a.vec = gs_aligned16(x) && gs_aligned16(t);
+  a.nblocks = gs_capped_blocks(a.n, GS_PEARSON_BLOCK_ELEMS, GS_PEARSON_MAX_BLOCKS);
   a.st = (PrStats*)tmp;
   a.part = (double*)((char*)tmp + gs_align(sizeof(PrStats)));
   return a;
@@ -220,7 +190,7 @@ extern "C" {
 
 size_t gs_pearson_tmp_bytes(int64_t n) {
   if (n < 2 || n > ((int64_t)1 << 40)) return 0;
-  return gs_align(sizeof(PrStats)) + gs_align((size_t)pr_blocks((size_t)n) * PR_Q * sizeof(double));
+  return gs_align(sizeof(PrStats)) + gs_align((size_t)gs_capped_blocks((size_t)n, GS_PEARSON_BLOCK_ELEMS, GS_PEARSON_MAX_BLOCKS) * PR_Q * sizeof(double));
 }
 
 int gs_pearson_fwd(const float* x, const float* t, int64_t n, int32_t form_a, int32_t form_b, void* tmp, float* out,
@@ -245,7 +215,7 @@ int gs_pearson_bwd(const float* x, const float* t, int64_t n, int32_t form_a, in
   if (!x || !t || !tmp || !dout_dev || (!grad_x && !grad_t)) return GS_E_NULL;
   if (grad_t && (form_a == GS_PEARSON_RECIP200 || form_b == GS_PEARSON_RECIP200)) return GS_E_UNSUPPORTED;
   PrArgs a = pr_args(x, t, n, form_a, form_b, (void*)tmp);
-  a.vec = a.vec && pr_aligned(grad_x) && pr_aligned(grad_t);
+  a.vec = a.vec && gs_aligned16(grad_x) && gs_aligned16(grad_t);
   hipStream_t s = (hipStream_t)stream;
   const size_t lanes = (a.n + 3) / 4;
   hipLaunchKernelGGL(pr_bwd_kernel, dim3((unsigned)((lanes + GS_BLOCK - 1) / GS_BLOCK)), dim3(GS_BLOCK), 0, s, a, dout_dev,

@@ -24,6 +24,7 @@
 // Every operation rounds on its own (-ffp-contract=off; divisions and the square root are the correctly rounded ones).
 #include "gs_common.h"
 #include "gs_haar.h"
+#include "gs_launch.h"
 
 namespace {
 
@@ -359,11 +360,6 @@ __global__ void __launch_bounds__(GS_BLOCK) ch_bwd_kernel(const float* __restric
   }
 }
 
-inline unsigned capped_blocks(int64_t n, int cap) {
-  const int64_t b = (n + GS_BLOCK - 1) / GS_BLOCK;
-  return (unsigned)(b < cap ? (b < 1 ? 1 : b) : cap);
-}
-
 }  // namespace
 
 extern "C" {
@@ -403,7 +399,7 @@ int gs_wef_maps(const float* pred, const float* gt, int32_t C, int32_t H, int32_
   } else {
     for (int k = 0; k < 3; k++) pl.p[k] = v.quarter[k];
   }
-  const unsigned nb = capped_blocks(n, WEF_NB);
+  const unsigned nb = (unsigned)gs_capped_blocks((size_t)n, GS_BLOCK, WEF_NB);
   if (all) hipLaunchKernelGGL(wef_bounds_kernel<true>, dim3(nb), dim3(GS_BLOCK), 0, s, pl, d, v.part);
   else hipLaunchKernelGGL(wef_bounds_kernel<false>, dim3(nb), dim3(GS_BLOCK), 0, s, pl, d, v.part);
   GS_LAUNCH_CHECK(s, 0);
@@ -449,7 +445,7 @@ int gs_charbonnier_fwd(const float* pred, const float* target, int64_t n, double
       ((uintptr_t)out & 3))
     return GS_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = capped_blocks(n, CH_NB);
+  const unsigned nb = (unsigned)gs_capped_blocks((size_t)n, GS_BLOCK, CH_NB);
   const float eps2 = (float)(epsilon * epsilon);  // the reference adds the Python float epsilon * epsilon to an fp32 tensor
   hipLaunchKernelGGL(ch_fwd_kernel, dim3(nb), dim3(GS_BLOCK), 0, s, pred, target, n, eps2, (double*)tmp);
   GS_LAUNCH_CHECK(s, 0);
@@ -466,7 +462,7 @@ int gs_charbonnier_bwd(const float* pred, const float* target, int64_t n, double
       ((uintptr_t)d_target & 3))
     return GS_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(ch_bwd_kernel, dim3(capped_blocks(n, 4096)), dim3(GS_BLOCK), 0, s, pred, target, n, epsilon * epsilon, grad_out,
+  hipLaunchKernelGGL(ch_bwd_kernel, dim3((unsigned)gs_capped_blocks((size_t)n, GS_BLOCK, 4096)), dim3(GS_BLOCK), 0, s, pred, target, n, epsilon * epsilon, grad_out,
                      d_pred, d_target);
   GS_LAUNCH_CHECK(s, 0);
   return GS_OK;

@@ -7,18 +7,13 @@ fp32 only, CUDA(HIP) tensors only.  An empty mask gives a NaN loss and a zero gr
 
 Nothing here synchronises with the host: the masked count stays on the device and the backward reads the incoming
 dL/dloss from device memory."""
-import ctypes as C
 
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
+from ._lib import gpu_tensors, hip_api, stream_of
 
 GLOBAL, L1 = 1, 2  # GS_DN_GLOBAL, GS_DN_L1
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _image(t, what, channels_one=True):
@@ -35,14 +30,8 @@ def _image(t, what, channels_one=True):
 
 
 def _ready(what, *tensors):
-    out = []
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
-        out.append(t.contiguous())
-    return out
+    """Tensor by tensor: the first tensor's dtype is reported before the second one's device."""
+    return [gpu_tensors(what, (t,), contiguous=True)[0] for t in tensors]
 
 
 def _patch_size(what, p, H, W):
@@ -101,7 +90,7 @@ class _PatchNormLoss(Function):
         mask = torch.empty((L, p * p), dtype=torch.uint8, device=dev) if want_mask else None
         tmp = _tmp(dev, H, W, p, 0)
         hip_api().call("depth_norm_fwd", input.data_ptr(), target.data_ptr(), H, W, p, float(margin), int(flags),
-                       tmp.data_ptr(), loss.data_ptr(), mask.data_ptr() if want_mask else None, _stream(input))
+                       tmp.data_ptr(), loss.data_ptr(), mask.data_ptr() if want_mask else None, stream_of(input))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(input, target)
             ctx.tmp = tmp
@@ -120,7 +109,7 @@ class _PatchNormLoss(Function):
         gloss = gloss.float().contiguous()
         grad = torch.empty_like(input)
         hip_api().call("depth_norm_bwd", input.data_ptr(), target.data_ptr(), H, W, p, margin, flags, ctx.tmp.data_ptr(),
-                       gloss.data_ptr(), grad.data_ptr(), _stream(input))
+                       gloss.data_ptr(), grad.data_ptr(), stream_of(input))
         _ws.give(ctx.tmp)
         ctx.tmp = None
         return grad.view(ctx.shape), None, None, None, None, None
@@ -142,7 +131,7 @@ class _DepthSmoothness(Function):
         loss = torch.empty((), dtype=torch.float32, device=depth.device)
         tmp = _tmp(depth.device, H, W, 0, 0)
         hip_api().call("depth_smooth_fwd", depth.data_ptr(), img.data_ptr(), Cn, H, W, tmp.data_ptr(), loss.data_ptr(),
-                       _stream(depth))
+                       stream_of(depth))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(depth, img)
             ctx.tmp = tmp
@@ -158,7 +147,7 @@ class _DepthSmoothness(Function):
         gloss = gloss.float().contiguous()
         grad = torch.empty_like(depth)
         hip_api().call("depth_smooth_bwd", depth.data_ptr(), img.data_ptr(), Cn, H, W, ctx.tmp.data_ptr(), gloss.data_ptr(),
-                       grad.data_ptr(), _stream(depth))
+                       grad.data_ptr(), stream_of(depth))
         _ws.give(ctx.tmp)
         ctx.tmp = None
         return grad.view(ctx.shape), None
@@ -188,7 +177,7 @@ class _DepthRegulariser(Function):
         tmp = _tmp(dev, H, W, p_local, p_global)
         cfg = (H, W, p_local, p_global, float(margin), float(w_local), float(w_global), float(w_smooth))
         hip_api().call("dng_depth_reg_fwd", depth.data_ptr(), mono.data_ptr(), *cfg, tmp.data_ptr(), parts.data_ptr(),
-                       ml.data_ptr() if want_masks else None, mg.data_ptr() if want_masks else None, _stream(depth))
+                       ml.data_ptr() if want_masks else None, mg.data_ptr() if want_masks else None, stream_of(depth))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(depth, mono)
             ctx.tmp = tmp
@@ -208,7 +197,7 @@ class _DepthRegulariser(Function):
         gtotal = gtotal.float().contiguous()
         grad = torch.empty_like(depth)
         hip_api().call("dng_depth_reg_bwd", depth.data_ptr(), mono.data_ptr(), *ctx.cfg, ctx.tmp.data_ptr(),
-                       gtotal.data_ptr(), grad.data_ptr(), _stream(depth))
+                       gtotal.data_ptr(), grad.data_ptr(), stream_of(depth))
         _ws.give(ctx.tmp)
         ctx.tmp = None
         return grad.view(ctx.shape), None, None, None, None, None, None, None, None

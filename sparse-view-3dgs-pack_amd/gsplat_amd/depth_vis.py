@@ -127,8 +127,7 @@ def _lut_on(device, rule):
 
 
 def _device_call(d, a, rule, want_composite, want_bounds):
-    from ._lib import hip_api
-    from .evaluate import _stream
+    from ._lib import hip_api, stream_of
     api = hip_api()
     H, W = int(d.shape[0]), int(d.shape[1])
     out = torch.empty((H, W, 3), dtype=torch.uint8, device=d.device)
@@ -139,7 +138,7 @@ def _device_call(d, a, rule, want_composite, want_bounds):
     tmp = torch.empty((nb,), dtype=torch.uint8, device=d.device)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     api.call("depth_vis", d.data_ptr(), ptr(a), H, W, RULES[rule], _lut_on(d.device, rule).data_ptr(), tmp.data_ptr(), nb,
-             out.data_ptr(), ptr(grey), ptr(comp), ptr(bounds), _stream(d))
+             out.data_ptr(), ptr(grey), ptr(comp), ptr(bounds), stream_of(d))
     return out, grey, comp, bounds
 
 

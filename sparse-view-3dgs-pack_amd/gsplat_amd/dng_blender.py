@@ -5,24 +5,14 @@ of the SH rows as render_sh evaluates it (gaussian_renderer/__init__.py:351-355)
 
 Nothing here synchronises with the host: the white rule's boolean-index statements (a gather through a boolean mask is a
 nonzero, so a blocking read-back) become counts kept in device memory; the mask and the target are formed once per camera.  fp32 and CUDA(HIP) tensors only, no CPU path."""
-import ctypes as C
 
 import torch
 
-from ._lib import hip_api
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+from ._lib import gpu_tensors, hip_api, stream_of
 
 
 def _ready(what, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in tensors:
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
+    gpu_tensors(what, tensors)
 
 
 def blender_background_mask(gt, threshold, mono=None, return_count=False):
@@ -48,7 +38,7 @@ def blender_background_mask(gt, threshold, mono=None, return_count=False):
         mono = mono.detach().contiguous()
         target = torch.empty_like(mono)
     api.call("blender_target", gt.data_ptr(), None if mono is None else mono.data_ptr(), H, W, float(threshold), tmp.data_ptr(),
-             mask.data_ptr(), count.data_ptr(), None if target is None else target.data_ptr(), _stream(gt))
+             mask.data_ptr(), count.data_ptr(), None if target is None else target.data_ptr(), stream_of(gt))
     out = (mask.view(torch.bool),) + (() if target is None else (target,)) + ((count,) if return_count else ())
     return out[0] if len(out) == 1 else out
 
@@ -78,7 +68,7 @@ def white_rule(colour, stat, opacity_raw, threshold, factor=0.1):
     cf = colour.detach().contiguous()
     counts = torch.empty((1,), dtype=torch.int32, device=cf.device)
     hip_api().call("dng_white_rule", cf.data_ptr(), stat.data_ptr(), opacity_raw.data_ptr(), P, float(threshold), float(factor),
-                   counts.data_ptr(), _stream(cf))
+                   counts.data_ptr(), stream_of(cf))
     return counts
 
 
@@ -122,5 +112,5 @@ def white_rule_sh(xyz, shs, active_sh_degree, campos, stat, opacity_raw, thresho
     colour = torch.empty((P, 3), dtype=torch.float32, device=xf.device) if return_colour else None
     hip_api().call("dng_white_rule_sh", xf.data_ptr(), None if dcf is None else dcf.data_ptr(), rf.data_ptr() if rf.numel() else None,
                    M, deg, cp.data_ptr(), stat.data_ptr(), opacity_raw.data_ptr(), P, float(threshold), float(factor),
-                   None if colour is None else colour.data_ptr(), counts.data_ptr(), _stream(xf))
+                   None if colour is None else colour.data_ptr(), counts.data_ptr(), stream_of(xf))
     return (counts, colour) if return_colour else counts

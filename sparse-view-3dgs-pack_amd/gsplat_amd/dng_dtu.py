@@ -6,25 +6,15 @@ the raw opacity in front of a densification (:218-230).
 Nothing here synchronises with the host: the reference's boolean-index statements (a nonzero, so a blocking read-back, each)
 become counts kept in device memory.  fp32 and CUDA(HIP) tensors only, no CPU path.  As in torch, a fill without an unmasked
 pixel gives NaN, and a penalty over an empty mask a NaN loss with a gradient of zeros."""
-import ctypes as C
 
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+from ._lib import gpu_tensors, hip_api, stream_of
 
 
 def _ready(what, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in tensors:
-        if t.dtype not in (torch.float32, torch.bool, torch.uint8):
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
+    gpu_tensors(what, tensors, dtypes=(torch.float32, torch.bool, torch.uint8))
 
 
 def _mask_bytes(what, x, mask):
@@ -67,7 +57,7 @@ def dtu_background_mask(gt, threshold, run=50, out=None, return_count=False):
     mask = torch.empty((1, H, W), dtype=torch.uint8, device=gt.device)
     count = torch.empty((1,), dtype=torch.int32, device=gt.device)
     hip_api().call("dtu_mask", gt.data_ptr(), H, W, float(threshold), int(run), mask.data_ptr(), count.data_ptr(), out.data_ptr(),
-                   _stream(gt))
+                   stream_of(gt))
     mask = mask.view(torch.bool)
     return (mask, out, count) if return_count else (mask, out)
 
@@ -84,7 +74,7 @@ class _MaskedMeanFill(Function):
         mean = torch.empty((1,), dtype=torch.float32, device=xf.device) if want_mean else None
         tmp = _tmp(n, xf.device)
         hip_api().call("masked_fill_fwd", xf.data_ptr(), mask.data_ptr(), n, tmp.data_ptr(), out.data_ptr(),
-                       None if mean is None else mean.data_ptr(), _stream(xf))
+                       None if mean is None else mean.data_ptr(), stream_of(xf))
         ctx.mask = mask
         if mean is not None:
             ctx.mark_non_differentiable(mean)
@@ -96,7 +86,7 @@ class _MaskedMeanFill(Function):
             return None, None, None
         g = g.float().contiguous()
         gx = torch.empty_like(g)
-        hip_api().call("masked_fill_bwd", g.data_ptr(), ctx.mask.data_ptr(), g.numel(), gx.data_ptr(), _stream(g))
+        hip_api().call("masked_fill_bwd", g.data_ptr(), ctx.mask.data_ptr(), g.numel(), gx.data_ptr(), stream_of(g))
         return gx, None, None
 
 
@@ -109,7 +99,7 @@ class _AlphaPenalty(Function):
         n = af.numel()
         out = torch.empty((1,), dtype=torch.float32, device=af.device)
         tmp = _tmp(n, af.device)
-        hip_api().call("alpha_penalty_fwd", af.data_ptr(), mask.data_ptr(), n, tmp.data_ptr(), out.data_ptr(), _stream(af))
+        hip_api().call("alpha_penalty_fwd", af.data_ptr(), mask.data_ptr(), n, tmp.data_ptr(), out.data_ptr(), stream_of(af))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(af)
             ctx.mask, ctx.tmp, ctx.shape = mask, tmp, alpha.shape   # tmp: the masked count, alive until the backward is enqueued
@@ -121,7 +111,7 @@ class _AlphaPenalty(Function):
         g = g.float().contiguous()
         ga = torch.empty_like(af)
         hip_api().call("alpha_penalty_bwd", af.data_ptr(), ctx.mask.data_ptr(), af.numel(), ctx.tmp.data_ptr(), g.data_ptr(),
-                       ga.data_ptr(), _stream(af))
+                       ga.data_ptr(), stream_of(af))
         ctx.tmp = None
         return ga.view(ctx.shape), None
 
@@ -181,12 +171,7 @@ def colour_rule(colour, stat, opacity_raw, black=None, white=None, value=None):
         if not (t.numel() == P and (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1))):
             raise ValueError("%s: %s must be [P] or [P,1] with P = %d, got shape %s" % (what, name, P, tuple(t.shape)))
     b, w = _rule(what, "black", black), _rule(what, "white", white)
-    for t in (colour, stat, opacity_raw):
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in (colour, stat, opacity_raw):
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
+    gpu_tensors(what, (colour, stat, opacity_raw))
     for name, t in (("stat", stat), ("opacity_raw", opacity_raw)):
         if not t.is_contiguous():
             raise ValueError("%s: %s is edited in place and must be contiguous" % (what, name))
@@ -194,5 +179,5 @@ def colour_rule(colour, stat, opacity_raw, black=None, white=None, value=None):
     cf = colour.detach().contiguous()
     counts = torch.empty((2,), dtype=torch.int32, device=cf.device)
     hip_api().call("dng_colour_rule", cf.data_ptr(), stat.data_ptr(), opacity_raw.data_ptr(), P, b[0], b[1], b[2], b[3],
-                   w[0], w[1], w[2], w[3], value, counts.data_ptr(), _stream(cf))
+                   w[0], w[1], w[2], w[3], value, counts.data_ptr(), stream_of(cf))
     return counts

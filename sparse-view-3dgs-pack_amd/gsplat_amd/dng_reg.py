@@ -8,31 +8,17 @@ each) become counts kept in device memory; the regulariser's forward is two laun
 each way, the mask one.  The weights travel as kernel arguments, the set sizes, the incoming gradient and the camera centres
 stay in device memory.  fp32 and CUDA(HIP) tensors only, no CPU path.  An empty opacity set gives a NaN loss with finite
 gradients, a Gaussian at the camera centre a NaN direction, as in torch."""
-import ctypes as C
 
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
+from ._lib import gpu_tensors, hip_api, stream_of
 
 RAW = 1  # GS_DNG_REG_RAW
 # what one workgroup sweeps at a time, and the largest grid (GS_DNG_REG_BLOCK_ROWS, GS_DNG_REG_MAX_BLOCKS of include/gsplat.h;
 # tests/test_dng_reg_cpu.py holds them to the header)
 BLOCK_ROWS = 1024
 MAX_BLOCKS = 1024
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _devices_then_dtypes(what, tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in tensors:
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
 
 
 def _rows3(what, name, t):
@@ -50,7 +36,7 @@ def check_regulariser(what, scaling, opacity):
         raise ValueError("%s: opacity must be [P] or [P,1], got shape %s" % (what, tuple(opacity.shape)))
     if opacity.shape[0] != P:
         raise ValueError("%s: scaling has %d rows and opacity has %d" % (what, P, opacity.shape[0]))
-    _devices_then_dtypes(what, (scaling, opacity))
+    gpu_tensors(what, (scaling, opacity))
     return P
 
 
@@ -58,7 +44,7 @@ def check_view_dirs(what, xyz, campos):
     P = _rows3(what, "xyz", xyz)
     if tuple(campos.shape) != (3,):
         raise ValueError("%s: campos must be [3], got shape %s" % (what, tuple(campos.shape)))
-    _devices_then_dtypes(what, (xyz, campos))
+    gpu_tensors(what, (xyz, campos))
     return P
 
 
@@ -68,7 +54,7 @@ def check_near_mask(what, xyz, centers):
         raise ValueError("%s: centers must be [K,3], got shape %s" % (what, tuple(centers.shape)))
     if centers.shape[0] < 1:
         raise ValueError("%s: needs at least one camera centre, got K = 0" % what)
-    _devices_then_dtypes(what, (xyz, centers))
+    gpu_tensors(what, (xyz, centers))
     return P, int(centers.shape[0])
 
 
@@ -86,7 +72,7 @@ class _Regulariser(Function):
         out = torch.empty((4,), dtype=torch.float32, device=dev)
         tmp = torch.empty((int(api.raw("dng_reg_tmp_bytes")(P)),), dtype=torch.uint8, device=dev)
         api.call("dng_reg_fwd", sf.data_ptr(), of.data_ptr(), P, float(w_shape), float(w_scale), float(w_opa), int(flags),
-                 int(max_blocks), tmp.data_ptr(), out.data_ptr(), _stream(sf))
+                 int(max_blocks), tmp.data_ptr(), out.data_ptr(), stream_of(sf))
         if any(ctx.needs_input_grad[:2]):
             ctx.save_for_backward(sf, of)
             ctx.tmp = tmp  # the record (P, n_hi, n_lo, weights): alive until the backward has been enqueued
@@ -105,7 +91,7 @@ class _Regulariser(Function):
         go = torch.empty_like(of) if ctx.needs_input_grad[1] else None
         hip_api().call("dng_reg_bwd", sf.data_ptr(), of.data_ptr(), P, flags, ctx.tmp.data_ptr(),
                        None if g_terms is None else g_terms.data_ptr(), None if g_total is None else g_total.data_ptr(),
-                       None if gs is None else gs.data_ptr(), None if go is None else go.data_ptr(), _stream(sf))
+                       None if gs is None else gs.data_ptr(), None if go is None else go.data_ptr(), stream_of(sf))
         ctx.tmp = None
         return (None if gs is None else gs.view(ctx.shapes[0]), None if go is None else go.view(ctx.shapes[1]),
                 None, None, None, None, None)
@@ -120,7 +106,7 @@ class _ViewDirs(Function):
         P = int(xyz.shape[0])
         xf, cf = xyz.detach().contiguous(), campos.detach().contiguous()
         out = torch.empty_like(xf)
-        hip_api().call("view_dirs_fwd", xf.data_ptr(), cf.data_ptr(), P, out.data_ptr(), _stream(xf))
+        hip_api().call("view_dirs_fwd", xf.data_ptr(), cf.data_ptr(), P, out.data_ptr(), stream_of(xf))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(xf, cf)
         return out
@@ -132,7 +118,7 @@ class _ViewDirs(Function):
         xf, cf = ctx.saved_tensors
         g = g.float().contiguous()
         gx = torch.empty_like(xf)
-        hip_api().call("view_dirs_bwd", xf.data_ptr(), cf.data_ptr(), int(xf.shape[0]), g.data_ptr(), gx.data_ptr(), _stream(xf))
+        hip_api().call("view_dirs_bwd", xf.data_ptr(), cf.data_ptr(), int(xf.shape[0]), g.data_ptr(), gx.data_ptr(), stream_of(xf))
         return gx, None
 
 
@@ -168,5 +154,5 @@ def near_camera_mask(xyz, centers, near):
     P, K = check_near_mask("near_camera_mask", xyz, centers)
     xf, cf = xyz.detach().contiguous(), centers.detach().contiguous()
     mask = torch.empty((P,), dtype=torch.bool, device=xf.device)
-    hip_api().call("near_mask", xf.data_ptr(), P, cf.data_ptr(), K, float(near), mask.data_ptr(), _stream(xf))
+    hip_api().call("near_mask", xf.data_ptr(), P, cf.data_ptr(), K, float(near), mask.data_ptr(), stream_of(xf))
     return mask

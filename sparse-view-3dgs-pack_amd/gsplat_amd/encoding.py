@@ -4,29 +4,20 @@ shencoder/src/shencoder.cu).  fp32 only; CPU tensors raise (no fallback).
 
 The grid's embedding gradient is the same bits on every run (a stable sort of the (slot, contribution) pairs and a
 fixed-order segmented sum, csrc/gs_encoding.hip), where the reference adds one float atomic per corner and channel."""
-import ctypes as C
 
 import numpy as np
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+from ._lib import gpu_tensors, hip_api, stream_of
 
 
 def _need_gpu(what, *tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
+    gpu_tensors(what, tensors, dtypes=None)
 
 
 def _f32(t, what):
-    if t.dtype != torch.float32:
-        raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
-    return t.contiguous()
+    return gpu_tensors(what, (t,), contiguous=True)[0]
 
 
 class _GridEncode(Function):
@@ -52,7 +43,7 @@ class _GridEncode(Function):
         dy_dx = torch.empty((B, L * D * Cdim), dtype=torch.float32, device=inputs.device) if calc_grad_inputs else None
         hip_api().call("grid_encode_fwd", inputs.data_ptr(), B, D, embeddings.data_ptr(), n_slots, Cdim, offsets.data_ptr(),
                        L, S, H, int(gridtype), int(bool(align_corners)), int(interpolation), outputs.data_ptr(),
-                       dy_dx.data_ptr() if dy_dx is not None else None, _stream(inputs))
+                       dy_dx.data_ptr() if dy_dx is not None else None, stream_of(inputs))
         ctx.save_for_backward(inputs, offsets, dy_dx)
         ctx.dims = (B, D, Cdim, L, S, H, int(gridtype), int(bool(align_corners)), int(interpolation), n_slots)
         return outputs
@@ -73,7 +64,7 @@ class _GridEncode(Function):
             api.call("grid_encode_bwd", grad.data_ptr(), inputs.data_ptr(), B, D, n_slots, Cdim, offsets.data_ptr(), L, S,
                      H, gridtype, align_corners, interp, dy_dx.data_ptr() if want_in else None,
                      grad_embeddings.data_ptr() if want_emb else None, grad_inputs.data_ptr() if want_in else None,
-                     tmp.data_ptr(), nbytes, _stream(grad))
+                     tmp.data_ptr(), nbytes, stream_of(grad))
         return grad_inputs, grad_embeddings, None, None, None, None, None, None, None
 
 
@@ -89,7 +80,7 @@ class _SHEncode(Function):
         inputs = inputs.float().contiguous()
         B = inputs.shape[0]
         outputs = torch.empty((B, degree * degree), dtype=torch.float32, device=inputs.device)
-        hip_api().call("sh_encode_fwd", inputs.data_ptr(), B, int(degree), outputs.data_ptr(), _stream(inputs))
+        hip_api().call("sh_encode_fwd", inputs.data_ptr(), B, int(degree), outputs.data_ptr(), stream_of(inputs))
         ctx.save_for_backward(inputs)
         ctx.degree = int(degree)
         ctx.calc_grad_inputs = bool(calc_grad_inputs)
@@ -103,7 +94,7 @@ class _SHEncode(Function):
         grad = grad.float().contiguous()
         grad_inputs = torch.empty_like(inputs)
         hip_api().call("sh_encode_bwd", grad.data_ptr(), inputs.data_ptr(), inputs.shape[0], ctx.degree,
-                       grad_inputs.data_ptr(), _stream(grad))
+                       grad_inputs.data_ptr(), stream_of(grad))
         return grad_inputs, None, None
 
 

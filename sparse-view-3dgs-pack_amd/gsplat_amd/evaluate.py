@@ -26,11 +26,10 @@ HERE still take images that already have the mask's size), and SSIM_sk here, on 
 
 Nothing here synchronises with the host: a view's numbers are float64 words in device memory, and Evaluator.result() is the
 one read-back of a whole test set."""
-import ctypes as C
 
 import torch
 
-from ._lib import hip_api
+from ._lib import hip_api, stream_of
 from .io import write_results_json  # noqa: F401  (the evaluation's files: results.json, per_view.json)
 
 CLAMP, QUANTISE, MASK_DTU = 1, 2, 4  # GS_EVAL_CLAMP, GS_EVAL_QUANTISE, GS_EVAL_MASK_DTU
@@ -38,10 +37,6 @@ WORDS = 8                            # GS_EVAL_WORDS: mse, psnr, ssim, l1, count
 C1, C2 = 0.01 ** 2, 0.03 ** 2        # utils/loss_utils.py (_ssim)
 _MSE, _PSNR, _SSIM, _L1, _COUNT, _SSIM_SK, _LPIPS = range(7)   # (words 5 and 6 are reserved = 0 unless ssim_sk / lpips are asked for)
 SK_WIN = 7                           # skimage's default win_size: smaller images raise there
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _image(t, what):
@@ -86,7 +81,7 @@ def _flags(mask, clamp, quantise):
 def _launch(render, gt, mask, Cn, H, W, flags, tmp, row, quantised):
     hip_api().call("eval_metrics", render.data_ptr(), gt.data_ptr(), None if mask is None else mask.data_ptr(), Cn, H, W,
                    int(flags), C1, C2, tmp.data_ptr(), tmp.numel(), row.data_ptr(),
-                   None if quantised is None else quantised.data_ptr(), _stream(render))
+                   None if quantised is None else quantised.data_ptr(), stream_of(render))
 
 
 def _tmp(device, Cn, H, W):
@@ -105,7 +100,7 @@ def _sk_tmp(device, Cn, H, W):
 def _launch_sk(render, gt, mask, Cn, H, W, flags, tmp, out):
     """out (one float64 word in device memory) <- SSIM_sk of the transformed pair; on the stream of _launch, after it"""
     hip_api().call("eval_ssim_sk", render.data_ptr(), gt.data_ptr(), None if mask is None else mask.data_ptr(), Cn, H, W,
-                   int(flags), tmp.data_ptr(), tmp.numel(), out.data_ptr(), _stream(render))
+                   int(flags), tmp.data_ptr(), tmp.numel(), out.data_ptr(), stream_of(render))
 
 
 def _launch_lpips(render, gt, mask, Cn, H, W, flags, weights, tmp, taps, word):

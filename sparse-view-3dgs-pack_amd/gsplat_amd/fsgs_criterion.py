@@ -14,10 +14,10 @@ the L1 sum falls back to gs_l1_fwd's float atomics, as in LGDWTCriterion.
 
 `FsgsCriterion.__call__` is the same loss from differentiable ops (LossOps.l1_loss / fused_ssim) - the un-fused path and the
 CPU checker's; the Pearson term is an injected callable there, because gsplat_amd.pearson has no CPU path."""
-import ctypes as C
 
 import torch
 
+from ._lib import stream_of
 from .losses import FusedLGDWTLoss, _FusedParams
 
 _NEG, _RECIP200 = 1, 2   # GS_PEARSON_NEG, GS_PEARSON_RECIP200
@@ -37,10 +37,6 @@ class _Ctx:
 
     def set_materialize_grads(self, v):
         pass
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
 
 
 class FusedFsgsLoss(torch.autograd.Function):
@@ -65,7 +61,7 @@ class FusedFsgsLoss(torch.autograd.Function):
         branch = torch.empty((), dtype=torch.int32, device=dev)
         tmp = torch.empty((int(api.raw("pearson_tmp_bytes")(n)),), dtype=torch.uint8, device=dev)
         api.call("pearson_fwd", xf.data_ptr(), tf.data_ptr(), n, _NEG, _RECIP200, tmp.data_ptr(), pout.data_ptr(),
-                 branch.data_ptr(), _stream(xf))
+                 branch.data_ptr(), stream_of(xf))
         loss = torch.add(photo, pout[0], alpha=float(depth_weight))   # (the node's one elementwise launch)
         ctx.crit, ctx.pctx, ctx.weight, ctx.n, ctx.depth_shape = crit, pctx, float(depth_weight), n, depth.shape
         ctx.tmp = tmp   # the statistics record: alive until the backward has been enqueued
@@ -92,7 +88,7 @@ class FusedFsgsLoss(torch.autograd.Function):
                 coef = (g.detach().reshape(1).to(torch.float32) * ctx.weight).contiguous()
             gx = torch.empty_like(xf)
             api.call("pearson_bwd", xf.data_ptr(), tf.data_ptr(), ctx.n, _NEG, _RECIP200, 0, ctx.tmp.data_ptr(), coef.data_ptr(),
-                     gx.data_ptr(), None, _stream(xf))
+                     gx.data_ptr(), None, stream_of(xf))
             g_depth = gx.view(ctx.depth_shape)
         if ctx.needs_input_grad[1]:
             g_image = FusedLGDWTLoss.backward(ctx.pctx, g, None)[1]

@@ -329,7 +329,7 @@ def resize_u8(img, size, return_planar=False):
     H, W, Cn = shape
     if is_tensor and img.is_cuda:
         from ._lib import hip_api
-        from .evaluate import _stream
+        from ._lib import stream_of
         api = hip_api()
         src = img.contiguous()
         out = torch.empty((H2, W2, Cn), dtype=torch.uint8, device=img.device)
@@ -340,7 +340,7 @@ def resize_u8(img, size, return_planar=False):
         tmp = torch.empty((nb,), dtype=torch.uint8, device=img.device) if nb else None
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         api.call("resize_bicubic_u8", src.data_ptr(), H, W, Cn, H2, W2, ptr(xb), ptr(xc), 0 if xc is None else xc.shape[1],
-                 ptr(yb), ptr(yc), 0 if yc is None else yc.shape[1], ptr(tmp), nb, out.data_ptr(), ptr(planar), _stream(img))
+                 ptr(yb), ptr(yc), 0 if yc is None else yc.shape[1], ptr(tmp), nb, out.data_ptr(), ptr(planar), stream_of(img))
     else:
         arr = (img.numpy() if is_tensor else np.asarray(img)).reshape(H, W, Cn)
         res = resize_u8_numpy(arr, (W2, H2))

@@ -10,15 +10,13 @@ import ctypes as C
 
 import torch
 
+from ._lib import stream_of
+
 BANDS = ("LL1", "LH1", "HL1", "HH1", "LL2", "LH2", "HL2", "HH2")
 
 # FusedLGDWTLoss writes the image gradient with ONE kernel and forms no clamped image (gs_lgdwt_fused_fwd / _bwd) where the
 # library has them and the shape allows (_FusedParams.fused_shape) - the same bits; False: the kernel sequence they replace.
 FUSED_PASSES = True
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream) if t.is_cuda else None
 
 
 def _c(t):
@@ -41,7 +39,7 @@ class LossOps:
             def forward(ctx, a, b):
                 a, b = _c(a), _c(b)
                 s = torch.zeros((1,), dtype=torch.float32, device=a.device)
-                ops.api.call("l1_fwd", a.data_ptr(), b.data_ptr(), a.numel(), s.data_ptr(), _stream(a))
+                ops.api.call("l1_fwd", a.data_ptr(), b.data_ptr(), a.numel(), s.data_ptr(), stream_of(a))
                 ctx.save_for_backward(a, b)
                 return (s / a.numel()).reshape(())
 
@@ -52,9 +50,9 @@ class LossOps:
                 coef = (g / a.numel()).reshape(1).contiguous()
                 ga = torch.empty_like(a)
                 if hasattr(ops.api, "_l1_bwd_dev"):
-                    ops.api.call("l1_bwd_dev", a.data_ptr(), b.data_ptr(), a.numel(), coef.data_ptr(), ga.data_ptr(), 0, _stream(a))
+                    ops.api.call("l1_bwd_dev", a.data_ptr(), b.data_ptr(), a.numel(), coef.data_ptr(), ga.data_ptr(), 0, stream_of(a))
                 else:
-                    ops.api.call("l1_bwd", a.data_ptr(), b.data_ptr(), a.numel(), 1.0, ga.data_ptr(), 0, _stream(a))
+                    ops.api.call("l1_bwd", a.data_ptr(), b.data_ptr(), a.numel(), 1.0, ga.data_ptr(), 0, stream_of(a))
                     ga = ga * coef
                 return ga, (-ga if ctx.needs_input_grad[1] else None)
 
@@ -65,7 +63,7 @@ class LossOps:
                 N, Cc, H, W = x.shape
                 h, w = (H + 1) // 2, (W + 1) // 2
                 outs = [torch.empty((N, Cc, h, w), dtype=torch.float32, device=x.device) for _ in range(4)]
-                ops.api.call("dwt_haar_fwd", x.data_ptr(), N * Cc, H, W, *[o.data_ptr() for o in outs], _stream(x))
+                ops.api.call("dwt_haar_fwd", x.data_ptr(), N * Cc, H, W, *[o.data_ptr() for o in outs], stream_of(x))
                 ctx.shape = (N, Cc, H, W)
                 return tuple(outs)
 
@@ -75,7 +73,7 @@ class LossOps:
                 gs = [None if g is None else _c(g) for g in (dll, dlh, dhl, dhh)]
                 ref = next(g for g in gs if g is not None)
                 dx = torch.empty((N, Cc, H, W), dtype=torch.float32, device=ref.device)
-                ops.api.call("dwt_haar_bwd", *[_p(g) for g in gs], N * Cc, H, W, dx.data_ptr(), _stream(ref))
+                ops.api.call("dwt_haar_bwd", *[_p(g) for g in gs], N * Cc, H, W, dx.data_ptr(), stream_of(ref))
                 return dx
 
         class _Dwt2L1(torch.autograd.Function):
@@ -86,7 +84,7 @@ class LossOps:
                 pred, gt = _c(pred), _c(gt)
                 Cc, H, W = pred.shape[-3:]
                 sums = torch.zeros((8,), dtype=torch.float32, device=pred.device)
-                ops.api.call("dwt2_l1_fwd", pred.data_ptr(), gt.data_ptr(), Cc, H, W, sums.data_ptr(), _stream(pred))
+                ops.api.call("dwt2_l1_fwd", pred.data_ptr(), gt.data_ptr(), Cc, H, W, sums.data_ptr(), stream_of(pred))
                 h1, w1 = (H + 1) // 2, (W + 1) // 2
                 h2, w2 = (h1 + 1) // 2, (w1 + 1) // 2
                 counts = torch.tensor([Cc * h1 * w1] * 4 + [Cc * h2 * w2] * 4, dtype=torch.float32, device=pred.device)
@@ -103,7 +101,7 @@ class LossOps:
                 Cc, H, W = pred.shape[-3:]
                 grad = torch.empty_like(pred)
                 ops.api.call("dwt2_l1_bwd", pred.data_ptr(), gt.data_ptr(), Cc, H, W, coef.data_ptr(), grad.data_ptr(),
-                             0, _stream(pred))
+                             0, stream_of(pred))
                 return grad, None, None
 
         class _PatchDwt(torch.autograd.Function):
@@ -113,7 +111,7 @@ class LossOps:
                 Cc, H, W = pred.shape[-3:]
                 sums = torch.zeros((3,), dtype=torch.float32, device=pred.device)
                 ops.api.call("patch_dwt_fwd", pred.data_ptr(), gt.data_ptr(), Cc, H, W, ps, mask.data_ptr(),
-                             sums.data_ptr(), _stream(pred))
+                             sums.data_ptr(), stream_of(pred))
                 hp = (ps + 1) // 2
                 n_sel = mask.sum().to(torch.float32)
                 denom = torch.clamp_min(n_sel * (Cc * hp * hp), 1.0)
@@ -129,7 +127,7 @@ class LossOps:
                 Cc, H, W = pred.shape[-3:]
                 grad = torch.empty_like(pred)
                 ops.api.call("patch_dwt_bwd", pred.data_ptr(), gt.data_ptr(), Cc, H, W, ctx.ps, mask.data_ptr(),
-                             coef.data_ptr(), grad.data_ptr(), 0, _stream(pred))
+                             coef.data_ptr(), grad.data_ptr(), 0, stream_of(pred))
                 return grad, None, None, None, None
 
         class _SSIMMap(torch.autograd.Function):
@@ -144,7 +142,7 @@ class LossOps:
                 else:
                     d1 = d2 = d3 = None
                 ops.api.call("ssim_fwd", img1.data_ptr(), img2.data_ptr(), B, Cc, H, W, float(C1), float(C2),
-                             smap.data_ptr(), _p(d1), _p(d2), _p(d3), _stream(img1))
+                             smap.data_ptr(), _p(d1), _p(d2), _p(d3), stream_of(img1))
                 if padding == "valid":
                     smap = smap[:, :, 5:-5, 5:-5]
                 if train:
@@ -166,7 +164,7 @@ class LossOps:
                 grad = torch.empty_like(img1)
                 ops.api.call("ssim_bwd", img1.data_ptr(), img2.data_ptr(), B, Cc, H, W, float(ctx.C1), float(ctx.C2),
                              dL_dmap.data_ptr(), d1.data_ptr(), d2.data_ptr(), d3.data_ptr(), grad.data_ptr(),
-                             _stream(img1))
+                             stream_of(img1))
                 return None, None, grad, None, None, None
 
         class _DepthL1(torch.autograd.Function):
@@ -178,7 +176,7 @@ class LossOps:
                 k = None if mask is None else _c(mask)
                 n = d.numel()
                 part = torch.empty((int(ops.api.raw("depth_l1_partials_count")(n)),), dtype=torch.float32, device=d.device)
-                ops.api.call("depth_l1", d.data_ptr(), m.data_ptr(), _p(k), n, part.data_ptr(), 0.0, None, None, _stream(d))
+                ops.api.call("depth_l1", d.data_ptr(), m.data_ptr(), _p(k), n, part.data_ptr(), 0.0, None, None, stream_of(d))
                 ctx.save_for_backward(d, m, k)
                 return (part.sum() / n).reshape(())
 
@@ -188,7 +186,7 @@ class LossOps:
                 coef = g.reshape(1).to(torch.float32).contiguous()
                 grad = torch.empty_like(d)
                 ops.api.call("depth_l1", d.data_ptr(), m.data_ptr(), _p(k), d.numel(), None, 1.0 / d.numel(), coef.data_ptr(),
-                             grad.data_ptr(), _stream(d))
+                             grad.data_ptr(), stream_of(d))
                 return grad, None, None
 
         self._L1, self._Haar, self._Dwt2L1, self._PatchDwt, self._SSIMMap = _L1, _Haar, _Dwt2L1, _PatchDwt, _SSIMMap
@@ -221,7 +219,7 @@ class LossOps:
         part = torch.empty((int(self.api.raw("depth_l1_partials_count")(n)),), dtype=torch.float32, device=d.device)
         grad = torch.empty_like(d)
         self.api.call("depth_l1", d.data_ptr(), m.data_ptr(), _p(k), n, part.data_ptr(), float(weight) / n, None, grad.data_ptr(),
-                      _stream(d))
+                      stream_of(d))
         return part.sum() * (float(weight) / n), grad
 
     def fused_ssim(self, img1, img2, padding="same", train=True):
@@ -261,7 +259,7 @@ class LossOps:
         out = torch.empty((N, 1, H, W), dtype=torch.float32, device=image.device)
         low = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=image.device)
         for n in range(N):
-            self.api.call("elf_map", image[n].data_ptr(), Cc, H, W, low.data_ptr(), out[n].data_ptr(), _stream(image))
+            self.api.call("elf_map", image[n].data_ptr(), Cc, H, W, low.data_ptr(), out[n].data_ptr(), stream_of(image))
         return out
 
     def patch_mask(self, elf_map, patch_size=128, percentile=0.2):
@@ -270,7 +268,7 @@ class LossOps:
         H, W = elf_map.shape[-2:]
         L = (H // patch_size) * (W // patch_size)
         means = torch.empty((L,), dtype=torch.float32, device=elf_map.device)
-        self.api.call("patch_means", elf_map.data_ptr(), H, W, patch_size, means.data_ptr(), _stream(elf_map))
+        self.api.call("patch_means", elf_map.data_ptr(), H, W, patch_size, means.data_ptr(), stream_of(elf_map))
         k = int(means.numel() * (1.0 - percentile))
         k = max(1, k)
         k = min(k, means.numel())
@@ -308,7 +306,7 @@ class FusedLGDWTLoss(torch.autograd.Function):
         api = ops.api
         raw, gt = _c(raw), _c(gt)
         Cc, H, W = raw.shape
-        st = _stream(raw)
+        st = stream_of(raw)
         if stage is not None:   # exposure -> clamp -> alpha; everything below sees pred (clamping it again changes nothing)
             stage.raw = raw
             raw = torch.empty_like(raw)
@@ -377,7 +375,7 @@ class FusedLGDWTLoss(torch.autograd.Function):
             return (None,) * 8
         api, params = ctx.ops.api, ctx.params
         Cc, H, W = raw.shape
-        st = _stream(raw)
+        st = stream_of(raw)
         # [c_l1, c_ssim, c_band x8, c_patch x3, ...] x upstream gradient; a caller that seeds the backward with
         # LossOps.unit_grad (the train step does) gets the coefficients as they are: no multiply kernel
         unit = ctx.ops._unit.get(g.device)

@@ -20,8 +20,8 @@ import os
 
 import torch
 
-from ._lib import hip_api
-from .evaluate import _check, _flags, _stream
+from ._lib import hip_api, stream_of
+from .evaluate import _check, _flags
 
 # torchvision.models.vgg16().features: the index of each convolution, its (Cin, Cout); the taps sit after relu1_2, relu2_2,
 # relu3_3, relu4_3, relu5_3 (networks.py:93: target_layers 4, 9, 16, 23, 30), a 2 x 2 pool in front of every block but the first
@@ -102,7 +102,7 @@ def pack_conv_weight(w):
     if n == 0:
         raise ValueError("conv3x3: weight %s is none of VGG16's eight (Cin, Cout) pairs" % (tuple(w.shape),))
     out = torch.empty((n,), dtype=torch.float32, device=w.device)
-    hip_api().call("lpips_pack_weights", w.data_ptr(), cin, cout, out.data_ptr(), _stream(w))
+    hip_api().call("lpips_pack_weights", w.data_ptr(), cin, cout, out.data_ptr(), stream_of(w))
     return out
 
 
@@ -115,7 +115,7 @@ def conv3x3_relu(x, w, b):
     if int(w.shape[1]) != cin or int(b.shape[0]) != cout:
         raise ValueError("conv3x3: x %s, w %s and b %s do not fit" % (tuple(x.shape), tuple(w.shape), tuple(b.shape)))
     y = torch.empty((N, cout, H, W), dtype=torch.float32, device=x.device)
-    hip_api().call("lpips_conv3x3_relu", x.data_ptr(), packed.data_ptr(), b.data_ptr(), N, cin, cout, H, W, y.data_ptr(), _stream(x))
+    hip_api().call("lpips_conv3x3_relu", x.data_ptr(), packed.data_ptr(), b.data_ptr(), N, cin, cout, H, W, y.data_ptr(), stream_of(x))
     return y
 
 
@@ -126,7 +126,7 @@ def maxpool2(x):
     if H < 2 or W < 2:
         raise ValueError("maxpool2: at least 2 x 2 (got %d x %d) - torch raises there too" % (H, W))
     y = torch.empty((N, Cn, H // 2, W // 2), dtype=torch.float32, device=x.device)
-    hip_api().call("lpips_maxpool2", x.data_ptr(), N * Cn, H, W, y.data_ptr(), _stream(x))
+    hip_api().call("lpips_maxpool2", x.data_ptr(), N * Cn, H, W, y.data_ptr(), stream_of(x))
     return y
 
 
@@ -144,7 +144,7 @@ def tap_distance(fx, fy, lin):
     tmp = torch.empty((int(api.raw("lpips_distance_tmp_bytes")(H, W)),), dtype=torch.uint8, device=fx.device)
     out = torch.empty((1,), dtype=torch.float64, device=fx.device)
     api.call("lpips_distance", fx.data_ptr(), fy.data_ptr(), lin.data_ptr(), Cn, H, W, tmp.data_ptr(), tmp.numel(),
-             out.data_ptr(), _stream(fx))
+             out.data_ptr(), stream_of(fx))
     return out[0]
 
 
@@ -164,7 +164,7 @@ def launch(render, gt, mask, Cn, H, W, flags, weights, tmp, out):
     """out (six float64 words in device memory) <- the five per-tap terms and their sum; arguments as evaluate._check left them"""
     ptrs = weights.on(render.device)[3]
     hip_api().call("lpips_vgg", render.data_ptr(), gt.data_ptr(), None if mask is None else mask.data_ptr(), Cn, H, W, int(flags),
-                   ptrs[0], ptrs[1], ptrs[2], tmp.data_ptr(), tmp.numel(), out.data_ptr(), _stream(render))
+                   ptrs[0], ptrs[1], ptrs[2], tmp.data_ptr(), tmp.numel(), out.data_ptr(), stream_of(render))
 
 
 def lpips_vgg(render, gt, weights, mask=None, clamp=False, quantise=False, return_taps=False, tmp=None):

@@ -8,12 +8,11 @@ reduction of the weight gradients) backward.
 Weights in torch.nn.Linear layout [out,in].  The backward recomputes the forward, so the node saves its inputs only; no
 activation reaches device memory.  fp32 and CUDA(HIP) tensors only, no CPU path.  The weight gradients are the same bits on
 every run."""
-import ctypes as C
 
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
+from ._lib import gpu_tensors, hip_api, stream_of
 
 # GS_DNG_* of include/gsplat.h (tests/test_dng_neural_cpu.py holds them to the header)
 ENC_X = 32
@@ -24,10 +23,6 @@ TILE_ROWS = 128
 MAX_BLOCKS = 256
 WEIGHT_SHAPES = ((HIDDEN, ENC_X), (HIDDEN, HIDDEN), (1 + GEO, HIDDEN), (HIDDEN, ENC_D + GEO), (3, HIDDEN))
 WEIGHT_NAMES = ("w_s0", "w_s1", "w_s2", "w_c0", "w_c1")
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def _ptr(t):
@@ -44,12 +39,7 @@ def _check(what, enc_x, enc_d, weights):
         if tuple(w.shape) != shape:
             raise ValueError("%s: %s must be %s, got shape %s" % (what, name, list(shape), tuple(w.shape)))
     every = [enc_x] + ([] if enc_d is None else [enc_d]) + list(weights)
-    for t in every:
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in every:
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
+    gpu_tensors(what, every)
     return int(enc_x.shape[0])
 
 
@@ -67,7 +57,7 @@ class _Heads(Function):
         sigma = torch.empty((B,), dtype=torch.float32, device=x.device)
         color = torch.empty((B, 3), dtype=torch.float32, device=x.device) if full else None
         wp = [w.data_ptr() for w in ws] + [None] * (5 - len(ws))
-        hip_api().call("dng_heads_fwd", x.data_ptr(), _ptr(d), B, *wp, sigma.data_ptr(), _ptr(color), int(max_blocks), _stream(x))
+        hip_api().call("dng_heads_fwd", x.data_ptr(), _ptr(d), B, *wp, sigma.data_ptr(), _ptr(color), int(max_blocks), stream_of(x))
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x, *([d] if full else []), *ws)
         ctx.full = full
@@ -99,7 +89,7 @@ class _Heads(Function):
         wp = [w.data_ptr() for w in ws] + [None] * (5 - len(ws))
         gwp = [_ptr(w) for w in gw] + [None] * (5 - len(gw))
         api.call("dng_heads_bwd", x.data_ptr(), _ptr(d), B, *wp, _ptr(g_sigma), _ptr(g_color), _ptr(gx), _ptr(gd), *gwp,
-                 tmp.data_ptr(), nbytes, ctx.max_blocks, _stream(x))
+                 tmp.data_ptr(), nbytes, ctx.max_blocks, stream_of(x))
         gw = gw + [None] * (5 - len(gw))
         return (gx, gd) + tuple(g if n else None for g, n in zip(gw, need[2:7])) + (None,)
 

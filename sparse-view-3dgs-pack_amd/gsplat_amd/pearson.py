@@ -5,12 +5,11 @@ whose branch is picked on the device.
 Nothing here synchronises with the host: the forward is two launches, the backward one; the chosen branch, the statistics
 and the incoming gradient all stay in device memory.  fp32 and CUDA(HIP) tensors only, no CPU path.  A constant sequence
 gives NaN and a zero gradient."""
-import ctypes as C
 
 import torch
 from torch.autograd import Function
 
-from ._lib import hip_api
+from ._lib import gpu_tensors, hip_api, stream_of
 
 ID, NEG, RECIP200 = 0, 1, 2  # GS_PEARSON_ID, GS_PEARSON_NEG, GS_PEARSON_RECIP200
 WRT_R = 1                    # GS_PEARSON_WRT_R
@@ -18,10 +17,6 @@ WRT_R = 1                    # GS_PEARSON_WRT_R
 # tests/test_fsgs_loss_cpu.py holds them to the header)
 BLOCK_ELEMS = 4096
 MAX_BLOCKS = 512
-
-
-def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
 def flat_pair(what, a, b, names, columns=False):
@@ -34,12 +29,7 @@ def flat_pair(what, a, b, names, columns=False):
         raise ValueError("%s: %s has %d elements and %s has %d" % (what, names[0], a.numel(), names[1], b.numel()))
     if a.numel() < 2:
         raise ValueError("%s: needs at least 2 elements, got %d" % (what, a.numel()))
-    for t in (a, b):
-        if not t.is_cuda:
-            raise RuntimeError("%s expects CUDA(HIP) tensors - there is no CPU path" % what)
-    for t in (a, b):
-        if t.dtype != torch.float32:
-            raise RuntimeError("%s: fp32 only (got %s)" % (what, t.dtype))
+    gpu_tensors(what, (a, b))
     return int(a.numel())
 
 
@@ -58,7 +48,7 @@ class _Pearson(Function):
         branch = torch.empty((), dtype=torch.int32, device=dev)
         tmp = torch.empty((int(api.raw("pearson_tmp_bytes")(n)),), dtype=torch.uint8, device=dev)
         api.call("pearson_fwd", xf.data_ptr(), tf.data_ptr(), n, form_a, form_b, tmp.data_ptr(), out.data_ptr(),
-                 branch.data_ptr(), _stream(xf))
+                 branch.data_ptr(), stream_of(xf))
         if any(ctx.needs_input_grad[:2]):
             ctx.save_for_backward(xf, tf)
             ctx.tmp = tmp  # the statistics record: alive until the backward has been enqueued
@@ -76,7 +66,7 @@ class _Pearson(Function):
         gx = torch.empty_like(xf) if ctx.needs_input_grad[0] else None
         gt = torch.empty_like(tf) if ctx.needs_input_grad[1] else None
         hip_api().call("pearson_bwd", xf.data_ptr(), tf.data_ptr(), n, form_a, form_b, flags, ctx.tmp.data_ptr(), g.data_ptr(),
-                       None if gx is None else gx.data_ptr(), None if gt is None else gt.data_ptr(), _stream(xf))
+                       None if gx is None else gx.data_ptr(), None if gt is None else gt.data_ptr(), stream_of(xf))
         ctx.tmp = None
         return (None if gx is None else gx.view(ctx.shapes[0]), None if gt is None else gt.view(ctx.shapes[1]), None, None,
                 None)

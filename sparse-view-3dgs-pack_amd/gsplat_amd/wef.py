@@ -130,9 +130,10 @@ def wef_maps_torch(pred, gt, all_bands=False):
 
 # --------------------------------------------------------------------------------------------------------------- device
 def _api_stream(t):
-    from ._lib import hip_api
-    from .evaluate import _stream
-    return hip_api(), _stream(t)
+    from ._lib import hip_api, stream_of
+    if not t.is_cuda:  # wef_maps_device and the Charbonnier function take the stream before any check of their own
+        raise ValueError("Expected a cuda device, but got: %s" % t.device)
+    return hip_api(), stream_of(t)
 
 
 def wef_maps_device(pred, gt, all_bands=False):
