@@ -25,7 +25,7 @@ __global__ void __launch_bounds__(64, (HAS_INVDEPTH || HAS_EXTRA) ? 3 : 4) rende
     const uint32_t* __restrict__ n_contrib, const uint32_t* __restrict__ tile_work,
     const uint32_t* __restrict__ tile_order, const float* __restrict__ dL_dpixels,
     const float* __restrict__ dL_invdepths, const float* __restrict__ dL_dextra, gs_row_t* __restrict__ grad_rows) {
-  __shared__ float4 s_a[WB];  // x, y, invdepth, -
+  __shared__ float4 s_a[WB];  // x, y, invdepth, - (not read; holds the record's remaining value, see the gather pipeline)
   __shared__ float4 s_c[WB];  // conic, opacity
   __shared__ float4 s_k[WB];  // rgb, 4th channel
   __shared__ uint32_t s_id[WB];
@@ -43,6 +43,14 @@ __global__ void __launch_bounds__(64, (HAS_INVDEPTH || HAS_EXTRA) ? 3 : 4) rende
   const uint2 range = ranges[tile];
   const int n = (int)(range.y - range.x);
   if (n == 0) return;
+
+  const int q0 = n - (int)lmax;  // entries q < q0 (counted from the back) are behind every pixel's last contributor
+  const int rounds = (n + WB - 1) / WB;
+  // the first needed batch's ids are requested before the pixel state below, the records right behind it (pipeline: see the loop)
+  const uint32_t* __restrict__ plast = point_list + range.y - 1;  // position q from the back = plast[-q]
+  const int i0 = q0 / WB;
+  uint32_t rid, idn;
+  rid = idn = plast[-min(i0 * WB + lane, n - 1)];
 
   // slot s = quadrant (s&1, s>>1); this lane's pixel inside every quadrant is (lane&7, lane>>3)
   const int px0 = tile_x * TILE_X + (lane & 7), py0 = tile_y * TILE_Y + (lane >> 3);
@@ -92,36 +100,29 @@ __global__ void __launch_bounds__(64, (HAS_INVDEPTH || HAS_EXTRA) ? 3 : 4) rende
   const int lane_slot = lr == 15 ? rq : (lr == 0 ? 4 + rq : (rq == 0 ? GR_CB : (rq == 1 ? GR_EXTRA : (rq == 2 ? GR_ID : GR_N))));
   const float lane_scale = lr == 15 ? rowscale0 : (lr == 0 ? rowscale1 : 1.0f);
   const bool lane_adds = lr == 15 || lr == 0 || (lr == 7 && live2);
-  const int q0 = n - (int)lmax;  // entries q < q0 (counted from the back) are behind every pixel's last contributor
-  const int rounds = (n + WB - 1) / WB;
 
-  // prefetch the first needed batch
+  // Two-deep software pipeline over the list, walked from its back (the forward kernel's, see there): at the top of round i
+  // the records of batch i (ids in rid) and the ids of batch i + 1 (idn) are in flight - one wait, before staging; behind
+  // the staging the records of batch i + 1 are issued from idn, then the ids of batch i + 2, and both stay outstanding under
+  // the loop.  Every lane gathers from a position clamped into the list, nothing is gathered past the last batch.
+  // s_a's 4th slot is read by nobody; it receives the record's remaining value so that no lane of a pending destination is
+  // dead in the loop (with a constant there the allocator re-used the lane as a temporary, and the write waited for every
+  // outstanding load).
   float4 ra, rc, rk;
-  uint32_t rid = 0;
-  ra = rc = rk = make_float4(0.f, 0.f, 0.f, 0.f);
   {
-    const int q = (q0 / WB) * WB + lane;
-    if (q < n) {
-      rid = point_list[range.y - q - 1];
-      const float4* rec = reinterpret_cast<const float4*>(&splat[rid]);
-      ra = rec[0]; rc = rec[1]; rk = rec[2];
-    }
+    const float4* rec = reinterpret_cast<const float4*>(&splat[rid]);
+    ra = rec[0]; rc = rec[1]; rk = rec[2];
   }
-  for (int i = q0 / WB; i < rounds; i++) {
+  if (i0 + 1 < rounds) idn = plast[-min((i0 + 1) * WB + lane, n - 1)];
+  const auto stage = [&]() {
     __syncthreads();  // (single wave) previous batch fully consumed
     s_id[lane] = rid;
-    s_a[lane] = make_float4(ra.x, ra.y, FSGS ? ra.z : ra.w, 0.f);
+    s_a[lane] = make_float4(ra.x, ra.y, FSGS ? ra.z : ra.w, FSGS ? ra.w : ra.z);
     s_c[lane] = blend_stage_conic(rc);  // (qa, qb, qc, opacity), see gs_blend.h
     s_k[lane] = FSGS ? make_float4(rk.x, rk.y, rk.z, 1.0f) : rk;
     __syncthreads();
-    {
-      const int q = (i + 1) * WB + lane;
-      if (q < n) {
-        rid = point_list[range.y - q - 1];
-        const float4* rec = reinterpret_cast<const float4*>(&splat[rid]);
-        ra = rec[0]; rc = rec[1]; rk = rec[2];
-      }
-    }
+  };
+  const auto blend_batch = [&](const int i) {
     const int cnt = min(WB, n - i * WB);
     const int jbeg = max(0, q0 - i * WB);
     for (int j = jbeg; j < cnt; j++) {
@@ -211,7 +212,20 @@ __global__ void __launch_bounds__(64, (HAS_INVDEPTH || HAS_EXTRA) ? 3 : 4) rende
       // which tiles came before it - one global_atomic_add_f64 instruction, twelve lanes, one 128-byte line
       if (lane_adds) atomicAdd(grad_rows + (size_t)s_id[j] * GR_STRIDE + lane_slot, (double)tot);
     }
+  };
+  // The last round is peeled so that the gather in the loop stands under no condition at all: a branch around it, even a
+  // wave-uniform one, leaves a join behind it, and the copies that merge the loaded registers there wait for the loads.
+  int i = i0;
+  for (; i + 1 < rounds; i++) {
+    stage();
+    rid = idn;
+    const float4* rec = reinterpret_cast<const float4*>(&splat[rid]);
+    ra = rec[0]; rc = rec[1]; rk = rec[2];
+    if (i + 2 < rounds) idn = plast[-min((i + 2) * WB + lane, n - 1)];
+    blend_batch(i);
   }
+  stage();
+  blend_batch(i);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

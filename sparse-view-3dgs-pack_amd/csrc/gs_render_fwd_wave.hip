@@ -79,15 +79,28 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
   }
 
   float stop_z = __builtin_inff();  // view depth of the entry at which the tile's last pixel saturated
+  // Two-deep software pipeline over the list.  At the top of round i the records of batch i are in flight towards
+  // ra / rc / rk and the ids of batch i + 1 towards idn: one wait, before staging.  Behind the staging the records of
+  // batch i + 1 are issued from idn, then the ids of batch i + 2, and both stay outstanding under the blend loop.
+  // Every lane gathers, from an index clamped into the list (lanes past the end repeat its last entry; their staged
+  // copies lie behind cnt and are never read), and nothing is gathered past the last batch.
+  // Two things keep the loads in flight, both seen in the ISA (DESIGN_APPENDIX "prefetch traps"): the assignments to the
+  // loop-carried registers stand under no condition (behind a branch the allocator loads into temporaries and copies
+  // them at the join, and a copy waits for its load), and no lane of a pending destination is dead in the loop (a dead
+  // lane is re-used as a temporary, and a write to a register that a load is about to fill waits for ALL loads on gfx9;
+  // here every loaded lane is staged, and where an instantiation has no use for one the compiler narrows the load).
+  const uint32_t* __restrict__ plist = point_list + range.x;
   float4 ra, rc, rk;
   ra = rc = rk = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (lane < n) {
-    const float4* rec = reinterpret_cast<const float4*>(&splat[point_list[range.x + lane]]);
+  uint32_t idn = 0;
+  if (rounds > 0) {
+    idn = plist[min(lane, n - 1)];
+    const float4* rec = reinterpret_cast<const float4*>(&splat[idn]);
     ra = rec[0]; rc = rec[1]; rk = rec[2];
+    if (rounds > 1) idn = plist[min(WB + lane, n - 1)];
   }
-  for (int i = 0; i < rounds; i++) {
-    // the whole tile is done (forward.cu:326-328)
-    if (!__any(fmaxf(fmaxf(T[0], T[1]), fmaxf(T[2], T[3])) > 0.f)) break;
+  const auto tile_alive = [&]() { return __any(fmaxf(fmaxf(T[0], T[1]), fmaxf(T[2], T[3])) > 0.f) != 0; };
+  const auto stage = [&]() {
     __syncthreads();  // single wave: previous batch fully consumed
     s_a[lane] = make_float4(ra.x, ra.y, FSGS ? ra.z : ra.w, ra.z);
     s_c[lane] = blend_stage_conic(rc);  // (qa, qb, qc, opacity), see gs_blend.h
@@ -109,13 +122,8 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
     }
     if (HAS_EXTRA) s_e[lane] = rk.w;
     __syncthreads();
-    {
-      const int nxt = (i + 1) * WB + lane;
-      if (nxt < n) {
-        const float4* rec = reinterpret_cast<const float4*>(&splat[point_list[range.x + nxt]]);
-        ra = rec[0]; rc = rec[1]; rk = rec[2];
-      }
-    }
+  };
+  const auto blend_batch = [&](const int i) {
     const int cnt = min(WB, n - i * WB);
     bool running = true;  // (wave-uniform; the outer loop's own check ends the tile when the batch loop has been left)
     for (int j = 0; j < cnt && running; j++) {
@@ -164,6 +172,21 @@ __global__ void __launch_bounds__(64) render_fwd_wave_kernel(const uint2* __rest
       running = __any(fmaxf(fmaxf(T[0], T[1]), fmaxf(T[2], T[3])) > 0.f);
       if (!running && !CULL) stop_z = a.w;
     }
+  };
+  // The last round is peeled so that the gather in the loop stands under no condition at all: a branch around it, even a
+  // wave-uniform one, leaves a join behind it, and the copies that merge the loaded registers there wait for the loads.
+  int i = 0;
+  for (; i + 1 < rounds; i++) {
+    if (!tile_alive()) break;  // the whole tile is done (forward.cu:326-328)
+    stage();
+    const float4* rec = reinterpret_cast<const float4*>(&splat[idn]);
+    ra = rec[0]; rc = rec[1]; rk = rec[2];
+    if (i + 2 < rounds) idn = plist[min((i + 2) * WB + lane, n - 1)];
+    blend_batch(i);
+  }
+  if (i + 1 == rounds && tile_alive()) {
+    stage();
+    blend_batch(i);
   }
   if (lane == 0) {
     // depth-limited emission (gs_tilecull.h): the list of this tile was cut at depth_limit[tile] (+ margin).  All entries
