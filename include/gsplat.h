@@ -1455,6 +1455,34 @@ int gs_invdepth_prepare(const void* src, int32_t src_dtype, int32_t H, int32_t W
                         int32_t apply_scale, float scale, float offset, float mask_value, float* out_invdepth /*[H2,W2]*/,
                         float* out_mask /*NULL ok*/, void* stream);
 
+/* ---- image ingest (csrc/gs_image_ingest.hip): one decoded image to what the reference's Camera keeps ----
+ * Additive entries (GS_ABI_VERSION unchanged).  in uint8 [H,W,C] interleaved, C = 3 (RGB), 4 (RGBA) or 2 (LA: out_u8 only).
+ *   GS_INGEST_COMPOSITE (C = 4 only; with GS_INGEST_WHITE onto white, else black): first, at the source size,
+ *     q = byte(trunc((c / 255 * (a / 255) + bg * (1 - a / 255)) * 255)) evaluated in double, every operation rounded on its own
+ *     (scene/dataset_readers.py:353-359); the image goes on as RGB, Ce = 3 channels, no alpha.  Otherwise Ce = C.
+ *   Resize to (W2, H2) by PIL.Image.resize's default filter, with the tables of gs_resize_bicubic_u8: RGB as there; LA / RGBA by
+ *     Pillow's premultiplied rule - t = c a + 128, c' = ((t >> 8) + t) >> 8 on the way into the first pass that runs, both passes
+ *     on the premultiplied bytes (alpha included), a == 0 or 255 -> c' else min(255, 255 c' / a) (integer division) on the way out
+ *     of the last.  A pass whose sizes agree is skipped; with both skipped the bytes are copied, without that round trip.
+ *   Outputs, each NULL ok but not all three: out_u8 [H2,W2,Ce]; out_image fp32 [3,H2,W2] = byte / 255, one correctly rounded
+ *     division (Camera.original_image); out_alpha fp32 [1,H2,W2] = alpha byte / 255, or 1 where the image has no alpha
+ *     (Camera.alpha_mask), with columns < W2 / 2 zeroed under GS_INGEST_ZERO_LEFT and columns >= W2 / 2 under
+ *     GS_INGEST_ZERO_RIGHT (train_test_exp, scene/cameras.py:50-54).
+ * At most two launches on `stream`; no atomics, no read-back, no host synchronisation; a table row whose run leaves the source
+ * reads nothing.  tmp: >= gs_image_ingest_tmp_bytes(...) bytes = the intermediate [H,W2,Ce] when both passes run, else 0.
+ * GS_E_NULL: in, all three outputs, a needed table or needed tmp missing; GS_E_SHAPE: C outside {2, 3, 4}, a size <= 0, an image
+ * above 2^30 bytes, unknown flag bits, GS_INGEST_COMPOSITE with C != 4, GS_INGEST_WHITE without it, C = 2 with out_image or
+ * out_alpha, ksize <= 0 for a pass that runs, or tmp_bytes too small. */
+#define GS_INGEST_COMPOSITE 1
+#define GS_INGEST_WHITE 2
+#define GS_INGEST_ZERO_LEFT 4
+#define GS_INGEST_ZERO_RIGHT 8
+size_t gs_image_ingest_tmp_bytes(int32_t H, int32_t W, int32_t C, int32_t H2, int32_t W2, int32_t flags);
+int gs_image_ingest(const uint8_t* in, int32_t H, int32_t W, int32_t C, int32_t H2, int32_t W2, const int32_t* xbounds,
+                    const int32_t* xcoef, int32_t kx, const int32_t* ybounds, const int32_t* ycoef, int32_t ky, int32_t flags,
+                    void* tmp, size_t tmp_bytes, uint8_t* out_u8 /*NULL ok*/, float* out_image /*NULL ok*/,
+                    float* out_alpha /*NULL ok*/, void* stream);
+
 /* ---- optional per-stage timing (HIP events recorded on the caller's stream around every kernel
  * group).  Off by default.  bench.py enables it over the timed region to get each kernel's average
  * launch duration on the stream it is launched on.  (No reference counterpart: the reference only

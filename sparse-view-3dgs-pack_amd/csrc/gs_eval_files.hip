@@ -18,21 +18,10 @@
 // in index order.  No atomics, no host synchronisation, the same bits on every run.
 #include "gs_common.h"
 #include "gs_eval_px.h"
+#include "gs_resize.h"  // rs_clip8, rs_run: shared with gs_image_ingest.hip
 
 namespace {
 
-constexpr int RS_PREC = 22;  // Pillow's PRECISION_BITS = 32 - 8 - 2
-
-__device__ __forceinline__ uint8_t rs_clip8(int32_t acc) {
-  const int32_t v = acc >> RS_PREC;
-  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-// a table row whose run leaves the source axis reads nothing (the byte is 0): a wrong table cannot make a load stray
-__device__ __forceinline__ int rs_run(const int32_t* __restrict__ bounds, int o, int ksize, int n_in, int& lo) {
-  lo = bounds[2 * o];
-  const int n = bounds[2 * o + 1];
-  return (lo >= 0 && n >= 0 && n <= ksize && lo <= n_in - n) ? n : 0;
-}
 __device__ __forceinline__ void rs_store_f32(float* __restrict__ outf, int C, int H2, int W2, int y, int j, uint8_t q) {
   const int x = j / C, c = j - x * C;
   outf[((size_t)c * H2 + y) * W2 + x] = __fdiv_rn((float)q, 255.0f);  // to_tensor

@@ -313,6 +313,8 @@ PROTOTYPES = {
     "depth_scales_tmp_bytes": (_SZ, [_I64]),
     "depth_scales": (C.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _P, _I32, _I32, _I32, _P, _SZ, _P, _P]),
     "invdepth_prepare": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, C.c_float, _I32, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "image_ingest_tmp_bytes": (_SZ, [_I32, _I32, _I32, _I32, _I32, _I32]),
+    "image_ingest": (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _I32, _P, _P, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
 }
 
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
@@ -368,6 +370,9 @@ DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_
                # depth priors from files: the host numpy path beside the wrapper is the arbiter (gsplat_amd/depth_priors.py,
                # restated with float64 forms in tests/depth_prior_reference.py)
                "depth_scales_tmp_bytes", "depth_scales", "invdepth_prepare",
+               # image ingest (composite, Pillow's resize with its alpha rule, the camera's planar image and alpha mask): the numpy
+               # path beside the wrapper is the arbiter (gsplat_amd/imageio.py, pinned by tests/golden/pil_resize_alpha.npz)
+               "image_ingest_tmp_bytes", "image_ingest",
                # the depth-only pass: a subset of gs_forward_render_fsgs / gs_backward_fsgs, compared against them on the GPU and
                # against the checker's FSGS generation under the reference's composition (tests/depth_pass_reference.py)
                "depth_forward", "depth_backward",

@@ -9,6 +9,10 @@ torchvision's save_image byte rule, and PIL.Image.resize's default filter on 8-b
                           bicubic of Pillow's Resample.c.  Device tensors go through gs_resize_bicubic_u8 (csrc/gs_eval_files.hip);
                           CPU tensors and numpy arrays through the same integer arithmetic in numpy.  The same bits either way.
   to_planar               torchvision's to_tensor of a decoded 8-bit image: fp32 [C,H,W] = byte / 255 (the kernel's same-size path)
+  resize_alpha_u8         Image.resize((W2, H2)) of a mode-LA / mode-RGBA image: the same filter on premultiplied bytes (the rule is
+                          stated above the function; tests/golden/pil_resize_alpha.npz pins it).  resize_u8 itself keeps refusing alpha
+  ingest_image            a decoded image -> the camera's (original_image, alpha_mask): NeRF-synthetic's composite, the resize,
+                          byte / 255, the mask (gs_image_ingest, csrc/gs_image_ingest.hip, for device tensors; gsplat_amd/scene.py)
 
 The resize restated (tests/golden/pil_resize.npz pins it to Pillow's bytes).  Per axis, in Python floats = C doubles:
   scale = in / out, filterscale = max(scale, 1), support = 2 filterscale, ksize = 2 ceil(support) + 1
@@ -358,3 +362,140 @@ def to_planar(u8):
     operation (a device-side div by a scalar may multiply by the reciprocal instead)."""
     H, W = int(u8.shape[0]), int(u8.shape[1])
     return resize_u8(u8, (W, H), return_planar=True)[1]
+
+
+# ------------------------------------------------------------------------------------------------------------ ingest
+# What lies between a decoded image file and the tensors a Camera keeps (LGDWT-GS/utils/camera_utils.py:loadCam,
+# scene/cameras.py:42-56): NeRF-synthetic's composite, Image.resize with Pillow's rule for images WITH alpha, byte / 255 and the
+# alpha mask.  Device tensors go through gs_image_ingest (csrc/gs_image_ingest.hip), arrays and CPU tensors through numpy: the
+# numpy path is the arbiter, tests/golden/pil_resize_alpha.npz pins it to Pillow's bytes.  (resize_u8 keeps refusing alpha.)
+# Pillow's rule for LA / RGBA (Image.resize converts to La / RGBa and back):
+#   premultiply      t = c a + 128, c' = ((t >> 8) + t) >> 8, alpha unchanged          (Convert.c: MULDIV255)
+#   both passes of the integer bicubic on the premultiplied bytes, alpha included
+#   un-premultiply   a == 0 or a == 255 -> c', else min(255, (255 c') // a)               (Convert.c: rgba2rgbA... la2lA)
+#   same size        the bytes are copied: Pillow returns self.copy() before it converts
+INGEST_COMPOSITE, INGEST_WHITE, INGEST_ZERO_LEFT, INGEST_ZERO_RIGHT = 1, 2, 4, 8   # GS_INGEST_*
+
+
+def premultiply_u8(img):
+    """uint8 numpy [H,W,2] / [H,W,4] -> the colour channels times alpha by Pillow's MULDIV255, alpha unchanged"""
+    a = img[:, :, -1:].astype(np.int64)
+    t = img[:, :, :-1].astype(np.int64) * a + 128
+    out = img.copy()
+    out[:, :, :-1] = ((t >> 8) + t) >> 8
+    return out
+
+
+def unpremultiply_u8(img):
+    """uint8 numpy [H,W,2] / [H,W,4] premultiplied -> straight alpha: a in (0, 255) divides, in integers, clipped at 255"""
+    a = img[:, :, -1:].astype(np.int64)
+    c = img[:, :, :-1].astype(np.int64)
+    q = np.minimum(255, (255 * c) // np.maximum(a, 1))
+    out = img.copy()
+    out[:, :, :-1] = np.where((a == 0) | (a == 255), c, q)
+    return out
+
+
+def resize_alpha_u8_numpy(img, size):
+    """uint8 numpy [H,W,2] (LA) or [H,W,4] (RGBA) -> Image.resize(size = (W2, H2))'s bytes, in numpy"""
+    W2, H2 = int(size[0]), int(size[1])
+    if (W2, H2) == (img.shape[1], img.shape[0]):
+        return np.ascontiguousarray(img).copy()
+    return unpremultiply_u8(resize_u8_numpy(premultiply_u8(img), (W2, H2)))
+
+
+def composite_u8_numpy(rgba, white_background):
+    """uint8 numpy [H,W,4] -> uint8 [H,W,3]: the bytes of dataset_readers.py:353-359 (io.composite_rgba times 255), in float64"""
+    norm = rgba.astype(np.float64) / 255.0
+    bg = 1.0 if white_background else 0.0
+    arr = norm[:, :, :3] * norm[:, :, 3:4] + bg * (1 - norm[:, :, 3:4])
+    return (arr * 255.0).astype(np.int64).astype(np.uint8)
+
+
+def _u8_image(img, who, channels):
+    is_tensor = torch.is_tensor(img)
+    if (img.dtype != torch.uint8) if is_tensor else (np.asarray(img).dtype != np.uint8):
+        raise ValueError("%s: uint8 only (got %s)" % (who, img.dtype))
+    shape = tuple(img.shape)
+    if len(shape) != 3 or shape[2] not in channels or shape[0] < 1 or shape[1] < 1:
+        raise ValueError("%s: [H,W,C] with C in %s (got %s)" % (who, "/".join(str(c) for c in channels), shape))
+    return is_tensor, shape
+
+
+def _ingest_call(src, size, flags, want_u8, want_planes):
+    """gs_image_ingest on a device tensor uint8 [H,W,C] -> (bytes or None, original_image or None, alpha_mask or None)"""
+    from ._lib import hip_api
+    from ._lib import stream_of
+    api = hip_api()
+    src = src.contiguous()
+    H, W, Cn = (int(v) for v in src.shape)
+    W2, H2 = size
+    Ce = 3 if flags & INGEST_COMPOSITE else Cn
+    dev = src.device
+    out = torch.empty((H2, W2, Ce), dtype=torch.uint8, device=dev) if want_u8 else None
+    image = torch.empty((3, H2, W2), dtype=torch.float32, device=dev) if want_planes else None
+    alpha = torch.empty((1, H2, W2), dtype=torch.float32, device=dev) if want_planes else None
+    xb, xc = _tables_on(dev, W, W2) if W2 != W else (None, None)
+    yb, yc = _tables_on(dev, H, H2) if H2 != H else (None, None)
+    nb = int(api.raw("image_ingest_tmp_bytes")(H, W, Cn, H2, W2, flags))
+    tmp = torch.empty((nb,), dtype=torch.uint8, device=dev) if nb else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    api.call("image_ingest", src.data_ptr(), H, W, Cn, H2, W2, ptr(xb), ptr(xc), 0 if xc is None else xc.shape[1], ptr(yb), ptr(yc),
+             0 if yc is None else yc.shape[1], flags, ptr(tmp), nb, ptr(out), ptr(image), ptr(alpha), stream_of(src))
+    return out, image, alpha
+
+
+def resize_alpha_u8(img, size):
+    """PIL-named: img.resize(size) with size = (W2, H2) and Pillow's default filter for a uint8 [H,W,2] (LA) or [H,W,4] (RGBA)
+    image.  A CUDA(HIP) tensor goes through gs_image_ingest and stays on the device; a CPU tensor or a numpy array takes the
+    numpy path and comes back as what it was.  The same bits either way."""
+    W2, H2 = int(size[0]), int(size[1])
+    if W2 < 1 or H2 < 1:
+        raise ValueError("resize_alpha_u8: size = (W2, H2) with both >= 1 (got %r)" % (size,))
+    is_tensor, _ = _u8_image(img, "resize_alpha_u8", (2, 4))
+    if is_tensor and img.is_cuda:
+        return _ingest_call(img, (W2, H2), 0, True, False)[0]
+    res = resize_alpha_u8_numpy(img.numpy() if is_tensor else np.asarray(img), (W2, H2))
+    return torch.from_numpy(res) if is_tensor else res
+
+
+def ingest_image(u8, size, white_background=None, train_test_exp=False, is_test_view=False, is_test_dataset=False):
+    """One decoded image, uint8 [H,W,3] or [H,W,4], -> (original_image fp32 [3,H2,W2], alpha_mask fp32 [1,H2,W2]) at
+    size = (W2, H2): what the reference's Camera keeps of it.
+      white_background  None: a COLMAP scene's image, resized as it is (an RGBA file's alpha becomes the mask, cameras.py:45-46).
+                        True / False: NeRF-synthetic - composite onto white / black first, at the source size, with the byte
+                        rule of dataset_readers.py:353-359 (an RGB file is given alpha 255, as its convert("RGBA") does); the
+                        image is RGB from there and the mask ones
+      train_test_exp, is_test_view, is_test_dataset   cameras.py:50-54: a test view keeps the half of its mask that its set scores
+    A CUDA(HIP) tensor goes through gs_image_ingest (at most two launches, no synchronisation) and the results stay on its
+    device; a CPU tensor gives CPU tensors and an array gives arrays through numpy - the same bits either way."""
+    W2, H2 = int(size[0]), int(size[1])
+    if W2 < 1 or H2 < 1:
+        raise ValueError("ingest_image: size = (W2, H2) with both >= 1 (got %r)" % (size,))
+    is_tensor, shape = _u8_image(u8, "ingest_image", (3, 4))
+    half = train_test_exp and is_test_view
+    if is_tensor and u8.is_cuda:
+        flags = 0
+        if white_background is not None:
+            if shape[2] == 3:
+                u8 = torch.cat((u8, torch.full(shape[:2] + (1,), 255, dtype=torch.uint8, device=u8.device)), dim=2)
+            flags = INGEST_COMPOSITE | (INGEST_WHITE if white_background else 0)
+        if half:
+            flags |= INGEST_ZERO_LEFT if is_test_dataset else INGEST_ZERO_RIGHT
+        _, image, alpha = _ingest_call(u8, (W2, H2), flags, False, True)
+        return image, alpha
+    arr = u8.numpy() if is_tensor else np.asarray(u8)
+    if white_background is not None:
+        if shape[2] == 3:
+            arr = np.concatenate((arr, np.full(shape[:2] + (1,), 255, dtype=np.uint8)), axis=2)
+        arr = composite_u8_numpy(arr, bool(white_background))
+    res = resize_u8_numpy(arr, (W2, H2)) if arr.shape[2] == 3 else resize_alpha_u8_numpy(arr, (W2, H2))
+    planes = np.ascontiguousarray(res.transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
+    image = np.ascontiguousarray(planes[:3])
+    alpha = planes[3:4].copy() if planes.shape[0] == 4 else np.ones((1, H2, W2), dtype=np.float32)
+    if half:
+        if is_test_dataset:
+            alpha[..., :W2 // 2] = 0
+        else:
+            alpha[..., W2 // 2:] = 0
+    return (torch.from_numpy(image), torch.from_numpy(alpha)) if is_tensor else (image, alpha)
