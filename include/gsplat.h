@@ -170,6 +170,12 @@ typedef struct GsScratch {
                                       GS_STATUS_CHECK - from its LAST kernel, with system-scope stores: no copy command, no extra
                                       launch on the stream.  Complete when the call's work has completed; a host that polls for
                                       the tag accepts the block when the check word matches, as with gs_forward_status. */
+  void* early_geometry_done;       /* optional (NULL: none), a hipEvent_t: gs_forward_geometry_early has run for EXACTLY this view,
+                                      these Gaussian rows, these buffers, this tile_depth_limit and this radii array, and the event
+                                      was recorded behind it.  gs_forward_geometry then waits for the event, resets the header and
+                                      runs the geometry kernel only over the 256-row blocks that call left out; everything downstream
+                                      is the single launch's, bit for bit.  Only with GsView.tile_cull = 2.  One-shot: the library
+                                      clears the field, so a forward repeated with the same struct runs in full. */
 } GsScratch;
 
 /* Gradient outputs of gs_backward (rasterize_points.cu:163-178).  All are written in full by
@@ -497,6 +503,21 @@ int gs_backward_step_fsgs(const GsView* view, const GsGaussians* g, const int32_
  * twice; two calls on the SAME scratch must not overlap in time (they would share the cursor). */
 int gs_step_uninstanced(const GsView* view, const GsGaussians* g, const int32_t* radii,
                         const GsScratch* scratch, const GsStepState* st, void* stream);
+
+/* Additive entry (GS_ABI_VERSION unchanged).  The early geometry pass of the NEXT view, in place: zeroes the region counters and
+ * runs gs_forward_geometry's kernel for `view` over the 256-row blocks in which GeomView.reached - as the previous forward
+ * blend on these buffers left it - flags no row.  Made to be issued on the stream that carries gs_step_uninstanced, right behind
+ * it: the rows of those blocks are final then (phase 2 of gs_backward_step writes parameters only in blocks with a reached row,
+ * and only whole float4s of a block's piece: every parameter array must start on 16 bytes), and the previous view's backward
+ * blend, chain and phase-2 kernels, which may still be running, read nothing of such a block but its zero flags.  The header and
+ * the list cursor are not touched.  `scratch`: the previous forward's geom / img / binning buffers and capacity, with the
+ * tile_depth_limit of `view`; `radii`: the array the next gs_forward_geometry will be given (not the previous view's, which its
+ * tail still reads).  Then record an event and hand it to that gs_forward_geometry as GsScratch.early_geometry_done - if, and only
+ * if, it is called for this very view, rows, buffers, limit table and radii, and nothing wrote the rows in between; otherwise
+ * call it as usual: it zeroes the counters again and overwrites every row, the early pass was wasted work.
+ * GsView.tile_cull = 2 only, and only while the forward blend fills the flags (GS_REACHED_SPLIT): GS_E_UNSUPPORTED otherwise. */
+int gs_forward_geometry_early(const GsView* view, const GsGaussians* g, const GsScratch* scratch, int32_t* radii,
+                              void* stream);
 
 /* Stage 2 of gs_backward on its own (parity export): the per-Gaussian chain rule from given sums of the blend
  * backward.  rows [P,16] FLOAT64 (device): mean2D.x, mean2D.y, conic.xx, conic.xy, conic.yy, opacity, r, g, b, depth slot,

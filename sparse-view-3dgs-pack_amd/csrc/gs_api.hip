@@ -103,23 +103,10 @@ int gs_scratch_bytes(int32_t P, int32_t W, int32_t H, int64_t R_capacity, size_t
   return GS_OK;
 }
 
-int gs_forward_geometry(const GsView* v, const GsGaussians* g, GsScratch* sc, int32_t* radii,
-                        int32_t* num_rendered_host, void* stream) {
-  int rc = check_args(v, g);
-  if (rc) return rc;
-  if (!sc || !sc->geom) return GS_E_NULL;
-  sc->binned = 0;  // a new geometry state invalidates whatever lists these buffers held (gs_forward_bin sets it again)
-  hipStream_t s = (hipStream_t)stream;
+// the geometry kernel's arguments for (view, Gaussians, scratch); with region binning also where its buckets and counters live
+static int geometry_args(const GsView* v, const GsGaussians* g, const GsScratch* sc, int32_t* radii, PreprocessArgs& a,
+                         RegionLayout& rl) {
   const int P = g->P;
-  if (sc->geom_bytes < geom_bytes((size_t)P)) return GS_E_SCRATCH;
-  GeomView gv = geom_view(sc->geom, (size_t)P);
-  if (P == 0) {
-    GS_HIP_CHECK(hipMemsetAsync(gv.hdr, 0, sizeof(GeomHeader), s));
-    if (num_rendered_host) GS_HIP_CHECK(hipMemcpyAsync(num_rendered_host, &gv.hdr->num_rendered, 4, hipMemcpyDeviceToHost, s));
-    return GS_OK;
-  }
-  if (!radii) return GS_E_NULL;
-  PreprocessArgs a;
   a.P = P;
   a.D = v->sh_degree;
   a.M = g->M;
@@ -156,20 +143,55 @@ int gs_forward_geometry(const GsView* v, const GsGaussians* g, GsScratch* sc, in
   a.rg_x = a.rg_y = 0;
   if (v->tile_cull == 2) {
     // region binning: the buckets live in the binning buffer, the counters in the image buffer - both must be here already
-    RegionLayout rl;
-    rc = region_layout(v, sc, rl);
+    const int rc = region_layout(v, sc, rl);
     if (rc) return rc;
     a.region_count = rl.count;
     a.region_bucket = rl.bucket;
     a.region_cap = rl.cap;
     a.rg_x = rl.rg_x;
     a.rg_y = rl.rg_y;
+  }
+  return GS_OK;
+}
+
+int gs_forward_geometry(const GsView* v, const GsGaussians* g, GsScratch* sc, int32_t* radii,
+                        int32_t* num_rendered_host, void* stream) {
+  int rc = check_args(v, g);
+  if (rc) return rc;
+  if (!sc || !sc->geom) return GS_E_NULL;
+  sc->binned = 0;  // a new geometry state invalidates whatever lists these buffers held (gs_forward_bin sets it again)
+  // (one-shot: a forward that is repeated with this struct runs in full)
+  void* const early_done = sc->early_geometry_done;
+  sc->early_geometry_done = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const int P = g->P;
+  if (sc->geom_bytes < geom_bytes((size_t)P)) return GS_E_SCRATCH;
+  GeomView gv = geom_view(sc->geom, (size_t)P);
+  if (P == 0) {
+    GS_HIP_CHECK(hipMemsetAsync(gv.hdr, 0, sizeof(GeomHeader), s));
+    if (num_rendered_host) GS_HIP_CHECK(hipMemcpyAsync(num_rendered_host, &gv.hdr->num_rendered, 4, hipMemcpyDeviceToHost, s));
+    return GS_OK;
+  }
+  if (!radii) return GS_E_NULL;
+  if (early_done && (v->tile_cull != 2 || !reached_marking())) return GS_E_UNSUPPORTED;
+  PreprocessArgs a;
+  RegionLayout rl = {};
+  rc = geometry_args(v, g, sc, radii, a, rl);
+  if (rc) return rc;
+  if (early_done) {
+    // gs_forward_geometry_early has served, for exactly this view and these rows, every block without a reached row and
+    // zeroed the counters in front of it: what is left is the header and the blocks the previous step's tail has just stepped
+    const hipError_t e = hipStreamWaitEvent(s, (hipEvent_t)early_done, 0);
+    if (e != hipSuccess) return (int)e;
+    launch_region_prepare(gv, rl.count, rl.rg_x * rl.rg_y, (uint32_t)P, s, 2);
+    GS_LAUNCH_CHECK(s, v->debug);
+  } else if (v->tile_cull == 2) {
     launch_region_prepare(gv, rl.count, rl.rg_x * rl.rg_y, (uint32_t)P, s);
     GS_LAUNCH_CHECK(s, v->debug);
   }
   {
     GS_PROF(ST_PREPROCESS_FWD, s);
-    launch_preprocess_fwd(a, gv, s);
+    launch_preprocess_fwd(a, gv, s, early_done ? 2 : 0);
   }
   GS_LAUNCH_CHECK(s, v->debug);
   if (v->tile_cull != 2) {  // (region binning needs no prefix sum: num_rendered is known when the lists are)
@@ -179,6 +201,27 @@ int gs_forward_geometry(const GsView* v, const GsGaussians* g, GsScratch* sc, in
   GS_LAUNCH_CHECK(s, v->debug);
   if (num_rendered_host)
     GS_HIP_CHECK(hipMemcpyAsync(num_rendered_host, &gv.hdr->num_rendered, 4, hipMemcpyDeviceToHost, s));
+  return GS_OK;
+}
+
+int gs_forward_geometry_early(const GsView* v, const GsGaussians* g, const GsScratch* sc, int32_t* radii, void* stream) {
+  int rc = check_args(v, g);
+  if (rc) return rc;
+  if (!sc || !sc->geom || !radii) return GS_E_NULL;
+  // (region binning only: the LSD path's geometry phase ends in a scan over every block; and only with the reached flags)
+  if (v->tile_cull != 2 || !reached_marking() || g->P == 0) return GS_E_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int P = g->P;
+  if (sc->geom_bytes < geom_bytes((size_t)P)) return GS_E_SCRATCH;
+  GeomView gv = geom_view(sc->geom, (size_t)P);
+  PreprocessArgs a;
+  RegionLayout rl = {};
+  rc = geometry_args(v, g, sc, radii, a, rl);
+  if (rc) return rc;
+  launch_region_prepare(gv, rl.count, rl.rg_x * rl.rg_y, (uint32_t)P, s, 1);
+  GS_LAUNCH_CHECK(s, v->debug);
+  launch_preprocess_fwd(a, gv, s, 1);
+  GS_LAUNCH_CHECK(s, v->debug);
   return GS_OK;
 }
 

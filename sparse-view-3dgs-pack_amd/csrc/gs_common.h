@@ -296,7 +296,9 @@ struct PreprocessArgs {
   uint32_t region_cap;
   int rg_x, rg_y;
 };
-int launch_preprocess_fwd(const PreprocessArgs& a, const GeomView& g, hipStream_t s);
+// block_filter (the early geometry pass): 0 = every 256-row block; 1 = only blocks in which GeomView.reached flags no row;
+// 2 = only blocks in which it flags one.  The flags are read as they stand when a workgroup starts; 1 never writes the header.
+int launch_preprocess_fwd(const PreprocessArgs& a, const GeomView& g, hipStream_t s, int block_filter = 0);
 int launch_scan_block_sums(const GeomView& g, int P, hipStream_t s);
 int launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t s);
 
@@ -316,7 +318,8 @@ static inline __host__ __device__ uint32_t region_capacity(int64_t capacity, int
   const int64_t c = regions > 0 ? capacity / regions : 0;
   return (uint32_t)(c > RG_MAX_ENTRIES ? RG_MAX_ENTRIES : (c < 0 ? 0 : c));
 }
-int launch_region_prepare(const GeomView& g, uint32_t* region_count, int regions, uint32_t P, hipStream_t s);
+// parts: 1 = zero the region counters, 2 = reset the header (list cursor, flags, P), 3 = both in one launch
+int launch_region_prepare(const GeomView& g, uint32_t* region_count, int regions, uint32_t P, hipStream_t s, int parts = 3);
 int launch_region_bin(const GeomView& g, const uint32_t* region_count, const uint2* region_bucket, uint32_t region_cap, int rg_x,
                       int rg_y, int grid_x, int grid_y, const float* tile_depth_limit, uint2* ranges, uint32_t* point_list,
                       int64_t capacity, hipStream_t s);

@@ -89,9 +89,25 @@ struct CoopWave {
   uint32_t tiles[64];  // with depth limits: accepted regions
 };
 
-template <bool COOP>
+// FILTER (the early geometry pass): which 256-row blocks a launch serves, decided from GeomView.reached as the
+// PREVIOUS view's forward blend left it and as it stands when the workgroup starts - PF_ALL: every block (today's code, no
+// flag is read); PF_UNREACHED: blocks in which no row is flagged (the early launch: their parameters are final once the
+// side stream's Adam kernel has ended); PF_REACHED: blocks with a flagged row (the late launch, behind the optimizer).  A
+// workgroup that is filtered out stores nothing.  The header words belong to the late launch whatever block 0's verdict is.
+#define PF_ALL 0
+#define PF_UNREACHED 1
+#define PF_REACHED 2
+template <bool COOP, int FILTER = PF_ALL>
 __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs a, GeomView g, int lds_floats) {
   const int idx = blockIdx.x * GS_BLOCK + threadIdx.x;
+  if constexpr (FILTER != PF_ALL) {
+    const int has_reached = __syncthreads_or((idx < a.P && g.reached[idx] != 0) ? 1 : 0);
+    if (FILTER == PF_REACHED && idx == 0) {
+      g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
+      g.hdr->pad[HDR_REACHED] = 0u;
+    }
+    if ((has_reached != 0) != (FILTER == PF_REACHED)) return;
+  }
   uint32_t tiles = 0, entries = TB_ENTRIES_UNKNOWN;
   const int T = a.grid_x * a.grid_y;
   // region binning: up to four bucket counters waiting to be bumped (selects, not an indexed array: that would live in
@@ -151,7 +167,7 @@ __global__ void __launch_bounds__(GS_BLOCK) preprocess_fwd_kernel(PreprocessArgs
   asm volatile("" : "+v"(op_in), "+v"(sc_in.x), "+v"(sc_in.y), "+v"(sc_in.z), "+v"(rq_in.x), "+v"(rq_in.y), "+v"(rq_in.z),
                "+v"(rq_in.w));
   const GsLdsFloatPtr lds_seg = (GsLdsFloatPtr)s_limit + (GS_LIMIT_TILES_IN_LDS ? T : 0);
-  if (idx == 0) {
+  if (FILTER == PF_ALL && idx == 0) {
     g.hdr->pad[HDR_LIMITED] = a.tile_depth_limit ? 1u : 0u;
     g.hdr->pad[HDR_REACHED] = 0u;  // (set again by the forward blend that fills g.reached)
   }
@@ -634,16 +650,23 @@ extern "C" int gs_region_coop(int32_t form) {
   return region_coop_form();
 }
 
-int launch_preprocess_fwd(const PreprocessArgs& a, const GeomView& g, hipStream_t s) {
+template <int FILTER>
+static void launch_preprocess_fwd_form(const PreprocessArgs& a, const GeomView& g, hipStream_t s) {
   const int nb = (a.P + GS_BLOCK - 1) / GS_BLOCK;
   const size_t lds = preprocess_limit_lds_floats(a);
   // (the cooperative form packs a region into 26 bits and a region row or column into 16)
   const bool coop = a.tile_cull == 2 && region_coop_form() && a.rg_x <= 0xFFFF && a.rg_y <= 0xFFFF &&
                     (long long)a.rg_x * a.rg_y <= (1ll << 26);
   if (coop)
-    hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
+    hipLaunchKernelGGL((preprocess_fwd_kernel<true, FILTER>), dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
   else
-    hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
+    hipLaunchKernelGGL((preprocess_fwd_kernel<false, FILTER>), dim3(nb), dim3(GS_BLOCK), 4 * lds, s, a, g, (int)lds);
+}
+// block_filter: 0 every block, 1 the blocks without a reached row, 2 the blocks with one (PF_*)
+int launch_preprocess_fwd(const PreprocessArgs& a, const GeomView& g, hipStream_t s, int block_filter) {
+  if (block_filter == PF_UNREACHED) launch_preprocess_fwd_form<PF_UNREACHED>(a, g, s);
+  else if (block_filter == PF_REACHED) launch_preprocess_fwd_form<PF_REACHED>(a, g, s);
+  else launch_preprocess_fwd_form<PF_ALL>(a, g, s);
   return 0;
 }
 int launch_scan_block_sums(const GeomView& g, int P, hipStream_t s) {

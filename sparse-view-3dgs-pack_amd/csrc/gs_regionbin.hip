@@ -29,11 +29,15 @@
 #define RB_WAVES (RB_THREADS / 64)
 #define RB_TILES (RG_TILES * RG_TILES)
 
+// PARTS: bit 0 = the counter half, bit 1 = the header half.  With an early geometry pass the counters are zeroed in front of it
+// (the previous view's region_bin_kernel is long done with them) and the header - which the previous step's tail still reads -
+// behind that tail, in front of the late launch.
+template <int PARTS>
 __global__ void __launch_bounds__(GS_BLOCK) region_prepare_kernel(GeomHeader* hdr, uint32_t* __restrict__ region_count,
                                                                    int regions, uint32_t P) {
   const int i = blockIdx.x * GS_BLOCK + threadIdx.x;
-  if (i < regions) region_count[(size_t)i * RG_COUNT_STRIDE] = 0u;
-  if (i == 0) {
+  if ((PARTS & 1) && i < regions) region_count[(size_t)i * RG_COUNT_STRIDE] = 0u;
+  if ((PARTS & 2) && i == 0) {
     hdr->num_rendered = 0u;  // the list cursor of region_bin_kernel
     hdr->overflow = 0u;
     hdr->trunc_failed = 0u;
@@ -223,9 +227,14 @@ __global__ void __launch_bounds__(GS_BLOCK) export_keys_region_kernel(const uint
     keys_sorted[i] = ((uint64_t)blockIdx.x << 32) | (uint64_t)__float_as_uint(splat[point_list[i]].depth);
 }
 
-int launch_region_prepare(const GeomView& g, uint32_t* region_count, int regions, uint32_t P, hipStream_t s) {
-  hipLaunchKernelGGL(region_prepare_kernel, dim3((regions + GS_BLOCK - 1) / GS_BLOCK > 0 ? (regions + GS_BLOCK - 1) / GS_BLOCK : 1),
-                     dim3(GS_BLOCK), 0, s, g.hdr, region_count, regions, P);
+int launch_region_prepare(const GeomView& g, uint32_t* region_count, int regions, uint32_t P, hipStream_t s, int parts) {
+  const dim3 grid((regions + GS_BLOCK - 1) / GS_BLOCK > 0 ? (regions + GS_BLOCK - 1) / GS_BLOCK : 1);
+  if (parts == 1)
+    hipLaunchKernelGGL(region_prepare_kernel<1>, grid, dim3(GS_BLOCK), 0, s, g.hdr, region_count, regions, P);
+  else if (parts == 2)
+    hipLaunchKernelGGL(region_prepare_kernel<2>, dim3(1), dim3(64), 0, s, g.hdr, region_count, regions, P);
+  else
+    hipLaunchKernelGGL(region_prepare_kernel<3>, grid, dim3(GS_BLOCK), 0, s, g.hdr, region_count, regions, P);
   return 0;
 }
 

@@ -66,6 +66,7 @@ class GsScratch(C.Structure):
         ("step_tag", C.c_void_p),
         ("tile_depth_limit_slack", C.c_void_p),
         ("status_host", C.c_void_p),
+        ("early_geometry_done", C.c_void_p),
     ]
 
 
@@ -154,6 +155,7 @@ PROTOTYPES = {
                                       _P, _P, _P, _F, _I32, _F, _F, _F, _I32, _P, _SZ, _P]),
     "step_uninstanced": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch),
                                    C.POINTER(GsStepState), _P]),
+    "forward_geometry_early": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), C.POINTER(GsScratch), _P, _P]),
     "backward_step": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P,
                                 C.POINTER(GsStepState), _P, _SZ, _P]),
     "backward_step_x": (C.c_int, [C.POINTER(GsView), C.POINTER(GsGaussians), _P, C.POINTER(GsScratch), _I64, _P, _P, _P,
@@ -320,7 +322,7 @@ PROTOTYPES = {
 # entry points only the device library has to provide (the CPU oracle is timed with a wall clock)
 # (and the fused 4-channel pass is a product-side fusion of two reference passes: its parity target is the
 # reference's two 3-channel passes, so the checker does not need it)
-DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_step_fsgs", "step_uninstanced", "export_tile_order", "export_tile_stop_depth", "forward_status", "forward_bin", "export_binning_region", "region_coop", "debug_blend_stats", "adam_step_gated", "tile_depth_limit_floats", "profile_enable", "profile_only", "profile_reset", "profile_stage_count", "profile_stage_name", "profile_read",
+DEVICE_ONLY = ("export_row_mask", "backward_step", "backward_step_x", "backward_step_fsgs", "step_uninstanced", "forward_geometry_early", "export_tile_order", "export_tile_stop_depth", "forward_status", "forward_bin", "export_binning_region", "region_coop", "debug_blend_stats", "adam_step_gated", "tile_depth_limit_floats", "profile_enable", "profile_only", "profile_reset", "profile_stage_count", "profile_stage_name", "profile_read",
                "forward_render_x", "backward_x", "forward_tile_order",
                # the image stage (exposure, clamp, alpha mask) and the exposures' Adam: the oracle restates them in torch
                "image_stage_partials_count", "image_stage_fwd", "image_stage_bwd", "exposure_adam",

@@ -44,7 +44,7 @@ class _Forward:
     """What the steps of one forward (RasterBackend.rasterize_gaussians) share: its view, Gaussians, buffers, outputs and
     camera state; on the GPU also its stream and pinned status block."""
     __slots__ = ("device", "stream", "view", "g", "P", "W", "H", "geom", "img", "radii", "out_color", "out_invdepth",
-                 "out_extra", "fsgs", "extra", "cache", "use_order", "use_limit", "static", "cur", "status")
+                 "out_extra", "fsgs", "extra", "cache", "use_order", "use_limit", "static", "cur", "status", "early")
 
     def __init__(self, device, stream, view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs, extra,
                  cache, use_order, use_limit, static):
@@ -54,19 +54,27 @@ class _Forward:
         self.out_color, self.out_invdepth, self.out_extra = out_color, out_invdepth, out_extra
         self.fsgs, self.extra = fsgs, extra
         self.cache, self.use_order, self.use_limit, self.static = cache, use_order, use_limit, static
-        self.cur = self.status = None
+        self.cur = self.status = self.early = None
 
 
 class _Last:
     """The last non-empty forward, as its backward finds it - by its geometry buffer, the object itself: the structs it built
     (and the tensors they point into) and whether it read raw rows.  When it armed the early side launch of a two-phase
     train step (RasterBackend.launch_uninstanced_early): that `step`, the forward's radii and image buffer, and once the
-    launch is issued its `done` event; a fused backward ends the arming."""
-    __slots__ = ("geom", "P", "view", "g", "keep", "raw", "step", "radii", "img", "done")
+    launch is issued its `done` event; a fused backward ends the arming.  `binning`, `cap`: the binning buffer of a deferred
+    region-binned forward and its capacity (what an early geometry pass of the next view would fill its buckets in)."""
+    __slots__ = ("geom", "P", "view", "g", "keep", "raw", "step", "radii", "img", "done", "binning", "cap")
 
     def __init__(self, geom, P, view, g, keep, raw):
         self.geom, self.P, self.view, self.g, self.keep, self.raw = geom, P, view, g, keep, raw
-        self.step = self.radii = self.img = self.done = None
+        self.step = self.radii = self.img = self.done = self.binning = self.cap = None
+
+
+class _Early:
+    """An early geometry pass (RasterBackend.request_early_geometry) that has been issued: the view it was computed for and the
+    rows it read (as the bytes of their structs), the caller's token, the buffers it wrote - the previous forward's geom / img /
+    binning and a radii array of its own -, the limit table it read, and the event recorded behind it."""
+    __slots__ = ("view", "g", "token", "P", "geom", "img", "binning", "cap", "radii", "limit", "limit_version", "event", "keep")
 
 
 class RasterBackend:
@@ -154,6 +162,12 @@ class RasterBackend:
         self.keep_workspace = False
         self.last_workspace = None
         self._zero_images = {}    # (device, H, W) -> [1,H,W] zeros (_zero_image)
+        # the early geometry pass (see EARLY_GEOMETRY): the caller's one-shot request for the view that comes next, its one-shot
+        # token of the forward that may use the result, the pass in flight (_Early), and what became of the passes so far
+        self.early_request = None
+        self.early_token = None
+        self._early = None
+        self.early_geometry_stats = dict(issued=0, used=0, stale=0)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self, device):
@@ -289,6 +303,7 @@ class RasterBackend:
                 self._update_hint(max(st[0], st[3] * regions), limited=True)
                 self.last_deferred_num_rendered = st[0]
             if not ok:
+                self.drop_early_geometry()   # (the step is repeated: what comes next is not the view the pass was made for)
                 self.depth_limit_stats["failed"] += 1
                 if st[2] != 0 or not regions:
                     d["cache"]["limit_ok"] = False
@@ -494,6 +509,99 @@ class RasterBackend:
     # forward from writing the flags) or False: the split stays on tiles_touched.
     REACHED_SPLIT = os.environ.get("GS_REACHED_SPLIT", "1") != "0"
 
+    # The early geometry pass (gs_forward_geometry_early): a train step that knows its next camera has the
+    # geometry kernel of THAT view run on the side stream, right behind the Adam stream of this step's unreached Gaussians, over the
+    # 256-row blocks without a reached row - their parameters are final there - and in place: into this forward's own buffers,
+    # which the next forward then takes over.  What stays in front of the next forward blend is one launch over the blocks the
+    # step's tail has just written.  Same lists, records, images and gradients, bit for bit.  GS_EARLY_GEOMETRY=0 or False: off.
+    EARLY_GEOMETRY = os.environ.get("GS_EARLY_GEOMETRY", "1") != "0"
+
+    def request_early_geometry(self, settings, camera_key, token):
+        """One-shot, before the forward of a fused two-phase train step: `settings` (a GaussianRasterizationSettings) and
+        `camera_key` of the view the caller will render NEXT with the same Gaussians.  `token`: anything that compares equal only
+        while nothing but this step's own backward has written the rows; the caller sets `early_token` to its current value before
+        that next forward, which uses the early result only if the two are equal and it is the very view, rows and limit table."""
+        self.early_request = (settings, camera_key, token) if self.EARLY_GEOMETRY else None
+
+    def _retire_early(self, e):
+        """An early pass nobody will use: the current stream is ordered behind it, so that its buffers - about to go back to the
+        allocator - are not handed to work that runs while it still writes them."""
+        self.early_geometry_stats["stale"] += 1
+        torch.cuda.current_stream(e.geom.device).wait_event(e.event)
+
+    def drop_early_geometry(self):
+        """Forget an early pass in flight (its view is not the one that comes next after all: a step that is being repeated)."""
+        if self._early is not None:
+            self._retire_early(self._early)
+        self._early = self.early_request = None
+
+    def join_early_geometry(self):
+        """Order the current stream behind an early pass in flight - it reads the parameter rows - and keep it (no-op without)."""
+        if self._early is not None:
+            torch.cuda.current_stream(self._early.geom.device).wait_event(self._early.event)
+
+    def _launch_early_geometry(self, f, side):
+        """Behind the side launch just issued on `side` for the forward `f` (_Last): the early pass its caller asked for, if
+        every condition holds.  Not for a capture-safe forward, under the test hooks that plant patterns in fresh buffers, rows
+        that are not the raw parameter arrays on the float4 grid, or a gradient-row workspace that still needs its clear launch
+        (that launch reads tiles_touched)."""
+        req, self.early_request = self.early_request, None
+        if self._early is not None:
+            self._retire_early(self._early)
+        self._early = None
+        if (req is None or not self.EARLY_GEOMETRY or not self.REACHED_SPLIT or os.environ.get("GS_REACHED_SPLIT", "1") == "0"
+                or f.binning is None or f.view.tile_cull != 2 or not f.raw or self.static_capacity is not None
+                or self.scratch_fill is not None or self.output_fill is not None or f.step.rows_override
+                or not hasattr(self.api, "_forward_geometry_early")):
+            return
+        rs, camera_key, token = req
+        device, g = f.geom.device, f.g
+        H, W = int(rs.image_height), int(rs.image_width)
+        if (H, W) != (f.view.image_height, f.view.image_width) or g.extra_channel or g.shs_rest or g.colors_precomp or g.cov3D_precomp:
+            return
+        if any((p or 0) % 16 for p in (g.means3D, g.shs, g.opacities, g.scales, g.rotations)):
+            return
+        ws = self._rows_ws.get((device.index, self.scratch_bytes(f.P, W, H, 0)[3]))
+        if ws is None or not ws[1]:
+            return
+        c = self._cam_cache.get((device.index, W, H, ("key", camera_key)))
+        if c is None or not c["limit_ok"]:   # (the next forward will not be a depth-limited one: it sizes its own buffers)
+            return
+        e = _Early()
+        e.keep = list(f.keep)
+        e.view = self._view(e.keep, device, rs.bg, rs.viewmatrix, rs.projmatrix, rs.campos, rs.tanfovx, rs.tanfovy, H, W,
+                            rs.scale_modifier, rs.sh_degree, rs.prefiltered, rs.antialiasing, rs.debug, tile_cull=2)
+        e.g, e.token, e.P, e.geom, e.img, e.binning, e.cap, e.limit = g, token, f.P, f.geom, f.img, f.binning, f.cap, c["limit"]
+        e.limit_version = e.limit._version   # (the forward's own last kernel rewrites the table through the library, in stream
+        #  order in front of this pass; a write through torch - a test that plants bounds - makes the pass stale)
+        e.radii = torch.empty((f.P,), dtype=torch.int32, device=device)
+        s = self._scratch(e.geom, e.img, e.binning, e.cap)
+        s.tile_depth_limit = e.limit.data_ptr()
+        self.api.call("forward_geometry_early", C.byref(e.view), C.byref(g), C.byref(s), e.radii.data_ptr(),
+                      C.c_void_p(side.cuda_stream))
+        e.event = torch.cuda.Event()
+        e.event.record(side)
+        self._early = e
+        self.early_geometry_stats["issued"] += 1
+
+    def _take_early_geometry(self, view, g, P, limit, request, static, fsgs, extra):
+        """The early pass in flight if the forward that starts now may use it (see request_early_geometry), else None; either
+        way it is not in flight any more."""
+        e, self._early = self._early, None
+        token, self.early_token = self.early_token, None
+        if e is None:
+            return None
+        # (... and only with the binning buffer this forward would have sized for itself)
+        hint = self._capacity_hint_limited if self._capacity_hint_limited > 0 else self._capacity_hint
+        cap = max(hint if hint > 0 else max(8 * P, 1 << 20), _regions(view.image_width, view.image_height))
+        if (self.EARLY_GEOMETRY and cap == e.cap and token is not None and token == e.token and request == "defer" and not static and not fsgs
+                and extra is None and limit is e.limit and limit._version == e.limit_version and self.fused_step is not None and self.scratch_fill is None
+                and self.output_fill is None and P == e.P and bytes(view) == bytes(e.view) and bytes(g) == bytes(e.g)
+                and self._arms_side_launch(self.fused_step, P)):
+            return e
+        self._retire_early(e)
+        return None
+
     def _two_phase(self, step, P):
         """Does the fused backward of `step` over P Gaussians run in two phases?  (Not its gradients-out form; with
         rows_override it does, and issues the side launch itself: see _arms_side_launch.)"""
@@ -512,6 +620,7 @@ class RasterBackend:
         if f is None or f.step is None or f.done is not None:
             return False
         f.done = self._launch_uninstanced(f.geom.device, f.view, f.g, f.radii, self._scratch(f.geom, f.img), f.step)
+        self._launch_early_geometry(f, self._side_stream(f.geom.device))
         return True
 
     def _structs(self, device, bg, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, viewmatrix,
@@ -624,12 +733,17 @@ class RasterBackend:
         g = self._gauss(keep, device, means3D, sh, colors_precomp, opacities, scales, rotations, cov3D_precomp, extra, raw=raw,
                         extra_gain=extra_gain, sh_rest=sh_rest)
 
-        gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
-        geom = torch.empty((gb,), **u8)
-        img = torch.empty((ib,), **u8)
-        if self.scratch_fill is not None:
-            self.scratch_fill("geom", geom)
-            self.scratch_fill("img", img)
+        early = self._take_early_geometry(view, g, P, limit, request, static, fsgs, extra) if device.type == "cuda" else None
+        if early is not None:
+            # (the previous forward's buffers, where the early pass has left most of this view's geometry, and its radii)
+            geom, img, radii = early.geom, early.img, early.radii
+        else:
+            gb, ib, _, _ = self.scratch_bytes(P, W, H, 0)
+            geom = torch.empty((gb,), **u8)
+            img = torch.empty((ib,), **u8)
+            if self.scratch_fill is not None:
+                self.scratch_fill("geom", geom)
+                self.scratch_fill("img", img)
         # (the train step's side launch and its backward describe the same view and the same Gaussians: they take these
         #  structs - and the tensors `keep` holds alive - instead of building them again)
         last = self._last = _Last(geom, P, view, g, keep, raw)
@@ -638,6 +752,7 @@ class RasterBackend:
             last.step, last.radii, last.img = step, radii, img
         f = _Forward(device, self._stream(device), view, g, P, W, H, geom, img, radii, out_color, out_invdepth, out_extra, fsgs,
                      extra, cache, cache is not None and self.order_hint_on, use_limit, static)
+        f.early = early
 
         if device.type != "cuda":
             nr = (C.c_int32 * 1)()
@@ -769,10 +884,24 @@ class RasterBackend:
         else:
             hint = self._capacity_hint_limited if (limited and self._capacity_hint_limited > 0) else self._capacity_hint
             cap = hint if hint > 0 else max(8 * f.P, 1 << 20)
+        early, f.early = f.early, None
+        if early is not None and (block is None or not limited or f.static):   # (not the forward it was taken for)
+            self._retire_early(early)
+            early = None
         for attempt in range(6):
-            cap = max(cap, regions)
-            binning = self._new_binning(f, cap)
+            if early is not None:
+                cap, binning = early.cap, early.binning
+            else:
+                cap = max(cap, regions)
+                binning = self._new_binning(f, cap)
             s = self._scratch_of(f, binning, cap, limit)
+            if early is not None:   # (the late launch: gs_forward_geometry waits for the event and serves the blocks left out)
+                s.early_geometry_done = early.event.cuda_event
+                self._early_done = early.event   # (kept alive until the next one replaces it)
+                self.early_geometry_stats["used"] += 1
+                early = None
+            if self._last is not None and self._last.geom is f.geom:
+                self._last.binning, self._last.cap = binning, cap
             self.api.call("forward_geometry", C.byref(f.view), C.byref(f.g), C.byref(s), f.radii.data_ptr(), None, f.stream)
             if block is not None:
                 self.api.call("forward_bin", C.byref(f.view), C.byref(f.g), C.byref(s), None, f.stream)
@@ -994,6 +1123,7 @@ class RasterBackend:
             self._join_tile_order(device)   # (the blend backward reads the launch order that kernel writes)
         arena, self.grad_arena = self.grad_arena, None
         step, self.fused_step = self.fused_step, None
+        self.early_request = None   # (a request the side launch did not take: nothing will)
         sh_rest, self.sh_rest = self.sh_rest, None
         sh_activated, self.sh_rest_activated = self.sh_rest_activated, False
         f = self._last if self._last is not None and self._last.geom is geomBuffer else None

@@ -1446,7 +1446,8 @@ class Trainer:
         return (k * self.world_size + self.rank) % len(self.cameras)
 
     def step(self, k):
-        return self._step_camera(self.camera_index(k), self.optimizer_step, ())
+        # (the camera of step k + 1 is known now: the step may start that view's geometry early, _request_early_geometry)
+        return self._step_camera(self.camera_index(k), self.optimizer_step, (), next_ci=self.camera_index(k + 1))
 
     def draw_cameras(self, seed):
         """train.py:106-111 for `world_size` ranks: one global step pops world_size cameras from the shared stack
@@ -1604,6 +1605,11 @@ class Trainer:
         g = getattr(self, "_graphed", None)
         if g is not None:
             g.settle()
+        # (an early geometry pass of the next view may still be reading the rows on the side stream: whatever the caller
+        #  enqueues next - a re-layout, a reset, another optimizer - is ordered behind it)
+        be = self._backend()
+        if be is not None and hasattr(be, "join_early_geometry"):
+            be.join_early_geometry()
         p, self._pending = getattr(self, "_pending", None), None
         if p is None:
             return
@@ -1617,6 +1623,8 @@ class Trainer:
                 return
         elif p["verdict"]():
             return
+        if be is not None and hasattr(be, "drop_early_geometry"):
+            be.drop_early_geometry()   # (a step that is repeated is not the view an early pass was made for)
         opt = self.model.optimizer
         opt.t, opt.seg_steps = p["counters"][0], dict(p["counters"][1])
         if p.get("exposure_steps") is not None:   # (its gated step changed nothing on the device either)
@@ -1776,16 +1784,39 @@ class Trainer:
                 and getattr(getattr(fn, "_impl", None), "backend", None) is not None
                 and type(self)._render_view is Trainer._render_view and type(self)._criterion_backward is Trainer._criterion_backward)
 
-    def _manual_step(self, ci, mask, backend, deferred):
-        """render -> criterion -> backward of the fused single-GPU step, by hand (see MANUAL_BACKWARD) -> (pkg, loss, parts,
-        the forward's deferred verdict or None)"""
+    def _raster_settings(self, ci):
         m, cam = self.model, self.cameras[ci]
-        fn = self.Rasterizer._fn
-        rs = self.Settings(
+        return self.Settings(
             image_height=int(cam.image_height), image_width=int(cam.image_width), tanfovx=math.tan(cam.FoVx * 0.5),
             tanfovy=math.tan(cam.FoVy * 0.5), bg=self.bg, scale_modifier=1.0, viewmatrix=cam.world_view_transform,
             projmatrix=cam.full_proj_transform, sh_degree=m.active_sh_degree, campos=cam.camera_center, prefiltered=False,
             debug=False, antialiasing=False)
+
+    # The early geometry pass (RasterBackend.EARLY_GEOMETRY): a step that is told its next camera (step(k): a pure function of k)
+    # asks the backend to run that view's geometry kernel behind its side launch.  The result is used only by a forward for that
+    # camera that finds the rows as this step's backward leaves them: the token below changes with every re-layout (generation,
+    # P), every optimizer step (Adam's counter), every write through torch to a parameter tensor or a camera matrix (their
+    # version counters: opacity reset, another optimizer) and with the SH degree.  Only for the plain eager fused step with
+    # deferred depth limits: not TrainerNIR, not the data-parallel forms, not rows_override, not a GraphedStep's capture.
+    def _early_token(self, ci):
+        m, cam = self.model, self.cameras[ci]
+        return (m.generation, m.P, m.active_sh_degree, id(m.optimizer), m.optimizer.t, m.flat._version,
+                tuple(p._version for p in m.params.values()),
+                tuple(t._version for t in (cam.world_view_transform, cam.full_proj_transform, cam.camera_center)))
+
+    def _early_geometry_ok(self, backend, fused_step, deferred):
+        m = self.model
+        return (fused_step and deferred and not m.with_nir and not self.RENDERS_NIR and self.world_size == 1
+                and getattr(self, "rows_override", None) is None and hasattr(backend, "request_early_geometry")
+                and backend.static_capacity is None and getattr(self, "_graphed", None) is None
+                and type(self)._render_view is Trainer._render_view)
+
+    def _manual_step(self, ci, mask, backend, deferred):
+        """render -> criterion -> backward of the fused single-GPU step, by hand (see MANUAL_BACKWARD) -> (pkg, loss, parts,
+        the forward's deferred verdict or None)"""
+        m = self.model
+        fn = self.Rasterizer._fn
+        rs = self._raster_settings(ci)
         backend.camera_key = ("trainer", self.uid, ci)   # (as GaussianRasterizer.forward does with its camera_key)
         backend.camera_key_limits = False
         empty = getattr(self, "_empty_cpu", None)
@@ -1885,7 +1916,7 @@ class Trainer:
                 torch.gt(radii, 0, out=m.grad_mask.view(torch.bool))
             self.exchange_and_step(optimizer_step, skip)
 
-    def _step_camera(self, ci, optimizer_step, skip, exposure_step=None):
+    def _step_camera(self, ci, optimizer_step, skip, exposure_step=None, next_ci=None):
         self.sync()
         m = self.model
         if exposure_step is None:
@@ -1903,6 +1934,9 @@ class Trainer:
                                and (m.exposure is not None or self.alpha_masks is not None))
         deferred = (fused_step or fused_dp) and self.depth_limit == "deferred" and getattr(self, "_coef_dev", None) is None \
             and (not self._image_extras() or stage_ok)
+        early_ok = self._early_geometry_ok(backend, fused_step, deferred)
+        if early_ok:   # (before this step's counters advance: the token of the rows as they stand)
+            backend.early_token = self._early_token(ci)
         if deferred:
             counters = (m.optimizer.t, dict(m.optimizer.seg_steps))
             backend.depth_limit_request = "defer"
@@ -1919,6 +1953,9 @@ class Trainer:
                 backend.fused_step.rows_override = rows.data_ptr()
             if self._use_stage and m.exposure is not None:   # the backward writes the view's verdict: the exposure's gate
                 backend.fused_step.fail_flag = m.exposure_optimizer.gate.data_ptr()
+            if early_ok and next_ci is not None:   # (the token of the rows as THIS step's backward will leave them)
+                backend.request_early_geometry(self._raster_settings(next_ci), ("trainer", self.uid, next_ci),
+                                               self._early_token(next_ci))
         elif backend is not None and hasattr(backend, "grad_arena") and not m.with_nir:
             m.arm_grad_arena(backend)
         mask = None if self.masks is None else self.masks[ci]
